@@ -24,10 +24,18 @@ streams (weak scaling, no collective on the data path). At N > 1 the line also c
 all-reduce (mod p) of the partial commitments in every step, through the C
 ABI's communicator (lf_dev_fold_step_sharded; latticeum_amd.dist).
 
-Beside the headline the line reports (same run, each its own timed batch):
-the reference ring Phi_72 at the real zkvm shape (the path with reference
-parity), the byte-equivalent d=1024 shape W=464, configs[4]'s d=4096 ring with
-kappa=64, the configs[1] NTT batch and batched Poseidon2.
+A plain run (`--gpus 1 --steps N --warmup W`) sets the workload up, warms up,
+times the N steps and prints the result line: `value` and `ms_per_step` and the
+contract's other keys. `--dump-outputs DIR` also writes what the last timed step
+computed as DIR/<name>.npy (dump_outputs), so two builds can be compared output
+for output; the inputs are seeded, the same on every run.
+
+With `--full` the line also reports (same run, each its own timed batch): the
+per-phase HIP-event times and roofline of the headline workload, the CPU
+baselines, the reference ring Phi_72 at the real zkvm shape (the path with
+reference parity), the byte-equivalent d=1024 shape W=464, configs[4]'s d=4096
+ring with kappa=64, the configs[1] NTT batch, batched Poseidon2, the sumcheck /
+Mz / fold() rows, at N > 1 the sharded fold, and the detail file.
 """
 from __future__ import annotations
 
@@ -61,9 +69,16 @@ def parse():
     ap.add_argument("--kappa", type=int, default=32)
     ap.add_argument("--streams", type=int, default=8,
                     help="concurrent step streams per GPU (independent witness / accumulator pairs)")
+    ap.add_argument("--full", action="store_true", default=False,
+                    help="beside the headline: the per-phase times and roofline (a timed pass of their own), the "
+                         "CPU baselines, the other shapes and rings, the NTT / Poseidon2 / sumcheck / Mz / fold() "
+                         "rows, at N > 1 the sharded fold, and the detail file; without it only the timed steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed step to DIR/<name>.npy "
+                         "(float64; dump_outputs)")
     ap.add_argument("--no-small-shape", dest="small", action="store_false", default=True,
-                    help="skip the W=464 / d=24 multi-stream measurements and the NTT / Poseidon2 timings "
-                         "reported beside the default workload")
+                    help="with --full: skip the W=464 / d=24 multi-stream measurements and the NTT / Poseidon2 "
+                         "timings reported beside the default workload")
     ap.add_argument("--cu-partition", action="store_true", default=False,
                     help="give each step stream its own contiguous block of CUs (lf_stream_create_cu_mask)")
     ap.add_argument("--cu-split", type=int, default=0,
@@ -78,9 +93,9 @@ def parse():
                          "launch (lf_dev_fold_step_batch: one pass over A for the group); 1: all streams")
     ap.add_argument("--cpu-baseline", dest="cpu", action="store_true", default=True)
     ap.add_argument("--no-cpu-baseline", dest="cpu", action="store_false")
-    ap.add_argument("--detail", default=DETAIL_DEFAULT,
+    ap.add_argument("--detail", default=None,
                     help="file for the full record (every side workload and phase); the printed line is the compact "
-                         "headline, which names this file")
+                         "headline, which names this file. Default: DETAIL_DEFAULT with --full, none without")
     return ap.parse_args()
 
 
@@ -497,18 +512,21 @@ class Workload:
                 j = (b % (S // g)) * g
                 self.ctxs[j].dev_fold_step_batch(self.ctxs[j + 1:j + g], self.sch, self.pr, self.W,
                                                  self.bufs[j:j + g])
+                self.last_stream = j + g - 1
             i = steps // g * g
             r = steps - i
             if r > 1:  # a partial last group is one smaller batch (every step still one full step)
                 j = ((steps // g) % (S // g)) * g
                 self.ctxs[j].dev_fold_step_batch(self.ctxs[j + 1:j + r], self.sch, self.pr, self.W,
                                                  self.bufs[j:j + r])
+                self.last_stream = j + r - 1
                 i = steps
         for i in range(i, steps):
             if comm is None:
                 self.ctxs[i % S].dev_fold_step(self.sch, self.pr, self.W, self.bufs[i % S])
             else:
                 self.ctxs[i % S].dev_fold_step_sharded(self.sch, self.pr, self.W, self.bufs[i % S], comm)
+            self.last_stream = i % S
 
     def timing(self, on):
         for c in self.ctxs:
@@ -552,18 +570,21 @@ def warmup_steps(wl, warmup, comm=None):
     return warmup
 
 
-def measure(LA, torch, LD, pg, world, wl, steps, warmup, comm=None):
+def measure(LA, torch, LD, pg, world, wl, steps, warmup, comm=None, phases=True, after_timed=None):
     """time `steps` fold steps of workload `wl` (after `warmup` untimed ones):
     barrier + device sync on both sides, max over ranks; every phase timed
     with HIP events on its launch stream inside the timed region. With several
     step streams the phases overlap, so their launch times would not be the
-    kernels' own: the phases are then timed in a second batch on one stream."""
+    kernels' own: the phases are then timed in a second batch on one stream.
+    phases=False: only the timed steps (no phase times, no second batch; the
+    report is empty). `after_timed()` runs once the timed steps are done and
+    checked, before any further pass."""
     S = len(wl.ctxs)
     # batched groups: the warmup covers at least one whole group, so the
     # batched contraction's first launch (code object load) is not timed
     wl.run(warmup_steps(wl, warmup, comm), comm)
     wl.sync()
-    serial = S == 1  # one stream: the timed steps are the phase pass
+    serial = S == 1 and phases  # one stream: the timed steps are the phase pass
     if serial:
         wl.timing(True)
     LD.barrier(pg)
@@ -579,6 +600,10 @@ def measure(LA, torch, LD, pg, world, wl, steps, warmup, comm=None):
     dt = time.perf_counter() - t0
     wl.sync()  # surfaces any decomposition overflow
     dt_max = LD.max_over_ranks(pg, dt)
+    if after_timed is not None:
+        after_timed()
+    if not phases:
+        return dt_max, ({}, None)
     if S > 1 and wl.batch and comm is None:
         # the phase pass of batched steps: every context on the first one's stream,
         # so the phases run one at a time and the contraction covers `group` steps
@@ -1187,6 +1212,46 @@ def zkvm_chain(LA, torch, ctx, M, S, d, n, t, m, steps=16, warmup=2):
             "last_vars_equal_replay": vars_equal}
 
 
+DUMP_SAMPLE = 1 << 18  # words kept of a larger output (the default shape's 13 outputs: 45 MB of float64)
+DUMP_SEED = 0x4C460020
+
+
+def _sample_index(numel, n, seed):
+    """n indices below numel, ascending: the first n outputs of SplitMix64(seed)
+    mod numel (fixed by `seed` alone, so two builds sample the same elements)"""
+    with np.errstate(over="ignore"):
+        x = np.uint64(seed) + np.arange(1, n + 1, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15)
+        x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        x ^= x >> np.uint64(31)
+    return np.sort(x % np.uint64(numel)).astype(np.int64)
+
+
+def dump_outputs(wl, torch, path):
+    """Write the outputs of the last step `wl` ran (lf_fold_step_bufs' output
+    buffers of the step stream that ran it: f_coeff, f, cm, wk, y, f0, f0_coeff,
+    w_ccs0, cm0, and the planes / fk / fk_coeff forms the workload keeps) as
+    `path`/<name>.npy, <name>_0 / <name>_1 for the two sides. An output of more
+    than DUMP_SAMPLE elements is sampled (_sample_index, seeded by the output's
+    position). Every file is float64 of shape (n, 2): the low and the high 32
+    bits of each u64 word, so the values are exact."""
+    keep = wl.keeps[wl.last_stream]
+    outs = []
+    for name in ("f_coeff", "f", "cm", "fk_coeff", "fk", "wk", "y", "f0", "f0_coeff", "w_ccs0", "cm0", "planes"):
+        v = keep[name]
+        if isinstance(v, list):
+            outs += [(f"{name}_{s}", t) for s, t in enumerate(v) if t is not None]
+        else:
+            outs.append((name, v))
+    p = Path(path)
+    p.mkdir(parents=True, exist_ok=True)
+    for k, (name, t) in enumerate(outs):
+        if t.numel() > DUMP_SAMPLE:
+            t = t[torch.from_numpy(_sample_index(t.numel(), DUMP_SAMPLE, DUMP_SEED + k)).to(t.device)]
+        w = t.cpu().numpy().view(np.uint64)
+        np.save(p / f"{name}.npy", np.stack([w & np.uint64(0xFFFFFFFF), w >> np.uint64(32)], axis=1).astype(np.float64))
+
+
 EXCLUDED = ("outside the timed step (other tiers): the Poseidon2 transcript and challenge derivation (rho is an "
             "input), linearization, the sumcheck provers and the Mz matrix-vector products")
 EXCLUDED_SHORT = "rho is an input; transcript, linearization, sumchecks, Mz outside the step"
@@ -1338,7 +1403,10 @@ def main():
     batched, group = wl.batch, wl.group
     warmup_run = warmup_steps(wl, args.warmup)
     K, L, N = wl.pr.K, wl.pr.L, wl.N
-    dt_max, (phases, roof) = measure(LA, torch, LD, pg, world, wl, args.steps, args.warmup)
+    detail = args.detail or (DETAIL_DEFAULT if args.full else None)
+    dump = (lambda: dump_outputs(wl, torch, args.dump_outputs)) if args.dump_outputs and rank == 0 else None
+    dt_max, (phases, roof) = measure(LA, torch, LD, pg, world, wl, args.steps, args.warmup, phases=args.full,
+                                     after_timed=dump)
     wl.close()
     del wl
     torch.cuda.empty_cache()
@@ -1347,7 +1415,7 @@ def main():
     out = None
     if rank == 0:
         cpu = None
-        if args.cpu and world == 1:
+        if args.full and args.cpu and world == 1:
             cpu = cpu_baseline(d, W, kappa)
         value = world * args.steps / dt_max
         out = {
@@ -1384,7 +1452,7 @@ def main():
             "phases": phases,
             "cpu_baseline": cpu,
         }
-    if args.small and args.d == 1024:
+    if args.full and args.small and args.d == 1024:
         ref = extra_shape(LA, torch, LD, pg, local, rank, world, 24, 19763, 32, 4, 128, 8,
                           "the reference ring Phi_72 = X^24 - X^12 + 1 at the real zkvm shape", batch=4)
         small = extra_shape(LA, torch, LD, pg, local, rank, world, 1024, 464, args.kappa, 4, 256, 16,
@@ -1401,7 +1469,7 @@ def main():
             out["small_shape"] = small
             out["configs4_d4096_kappa64"] = c4
             out["side_ops"] = ops
-    if world > 1:
+    if args.full and world > 1:
         # the sharded fold is the only part with a collective on the data path
         # (its own RCCL communicator): a rank stuck in it must not cost the
         # headline line, so past SHARDED_LIMIT_S rank 0 prints the line with the
@@ -1412,7 +1480,7 @@ def main():
         def give_up():
             if out is not None:
                 out["sharded_fold"] = {"error": f"timeout after {SHARDED_LIMIT_S} s"}
-                emit(out, args.detail)
+                emit(out, detail)
             sys.stderr.flush()
             os._exit(0)
 
@@ -1427,7 +1495,7 @@ def main():
         if out is not None:
             out["sharded_fold"] = sh
     if out is not None:
-        emit(out, args.detail)
+        emit(out, detail)
     LD.finalize(pg)
     return out
 

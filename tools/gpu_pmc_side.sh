@@ -1,12 +1,13 @@
 #!/bin/bash
 # PMC passes on the side ops alone (tools/side_ops_run.py): FETCH_SIZE and
 # WRITE_SIZE in passes of their own, then one SQ pass; summarised into
-# gpurun_out/pmc_side/pmc_{traffic,sq}_side_ops.json and profiles/ (bench.side_ops reads
+# $OUT/pmc_side/pmc_{traffic,sq}_side_ops.json and profiles/ (bench.side_ops reads
 # them back while the kernel sources still hash the same)
 cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
-mkdir -p gpurun_out
-O=gpurun_out/pmc_side
+export OUT=${OUT:-bench_out}  # where the logs and records go
+mkdir -p $OUT
+O=$OUT/pmc_side
 rm -rf $O && mkdir -p $O
 CFG='{"side_ops": true}'
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE -d $O/fetch -o run --output-format csv -- python3 tools/side_ops_run.py \

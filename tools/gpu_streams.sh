@@ -2,12 +2,13 @@
 # stream / batch count A/B on the reference ring, W = 464 and the headline
 cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
-mkdir -p gpurun_out
+export OUT=${OUT:-bench_out}  # where the logs and records go
+mkdir -p $OUT
 TAG=${1:-st}
 run() {  # name, args
-  timeout -k 10 300 python -u bench.py --no-small-shape --no-cpu-baseline $2 > gpurun_out/bench_${TAG}_$1.log 2>&1 || return 1
+  timeout -k 10 300 python -u bench.py --full --no-small-shape --no-cpu-baseline $2 > $OUT/bench_${TAG}_$1.log 2>&1 || return 1
   python3 -c "
-import json; d=json.loads([l for l in open('gpurun_out/bench_${TAG}_$1.log') if l.startswith('{')][-1])
+import json; d=json.loads([l for l in open('$OUT/bench_${TAG}_$1.log') if l.startswith('{')][-1])
 print('$1', round(d['value'],2), round(d['ms_per_step'],3))"
 }
 R="--d 24 --w 19763 --steps 128 --warmup 8"

@@ -2,11 +2,12 @@
 # W = 464: 4 streams in pairs vs one batch of 4, alternating
 cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
-mkdir -p gpurun_out
+export OUT=${OUT:-bench_out}  # where the logs and records go
+mkdir -p $OUT
 run() {  # name, args
-  timeout -k 10 300 python -u bench.py --no-small-shape --no-cpu-baseline $2 > gpurun_out/bench_wb_$1.log 2>&1 || return 1
+  timeout -k 10 300 python -u bench.py --full --no-small-shape --no-cpu-baseline $2 > $OUT/bench_wb_$1.log 2>&1 || return 1
   python3 -c "
-import json; d=json.loads([l for l in open('gpurun_out/bench_wb_$1.log') if l.startswith('{')][-1])
+import json; d=json.loads([l for l in open('$OUT/bench_wb_$1.log') if l.startswith('{')][-1])
 print('$1', round(d['value'],2), round(d['ms_per_step'],3))"
 }
 S="--w 464 --steps 256 --warmup 16"

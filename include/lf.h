@@ -612,6 +612,13 @@ const uint64_t *lf_ccs_c_device(const lf_ccs *M);
  * every slot, zero elsewhere -- the zkvm's R1CS-derived matrices), which the Mz
  * products then read as one word per entry; else 0 */
 int lf_ccs_is_scalar(const lf_ccs *M);
+/* 1 if lf_ccs_create kept copies of the ring-valued entries in the row-merged and
+ * transposed orders (the challenged products and the Mz weights then read their values
+ * sequentially), else 0: a scalar-valued CCS, one whose two copies exceed
+ * LATTICEUM_AMD_CCS_REORDER_BYTES (decimal bytes, read by every lf_ccs_create; 0: no
+ * copies; unset: 16 GiB), or one whose copies could not be allocated -- those products
+ * then gather the values through the entry indices, with the same results */
+int lf_ccs_is_reordered(const lf_ccs *M);
 /* out[r] = 1 if row r of M_j holds an entry (so MLE(M_j z) may be nonzero there), else 0; m bytes */
 int lf_ccs_row_live(const lf_ccs *M, int j, uint8_t *out);
 /* tracing spans of lf_fold_prove (the reference's #[instrument] spans): wall ms per

@@ -532,6 +532,12 @@ class CCSMatrices:
         """every entry a scalar (lf_ccs_is_scalar): the products read one word per entry"""
         return bool(self.lib.lf_ccs_is_scalar(self.h))
 
+    @property
+    def reordered(self) -> bool:
+        """copies of the ring-valued entries in the row-merged and transposed orders are
+        kept (lf_ccs_is_reordered); otherwise those products gather through the indices"""
+        return bool(self.lib.lf_ccs_is_reordered(self.h))
+
     def row_live(self, j: int, m: int):
         """which rows of M_j hold an entry (lf_ccs_row_live): m bools"""
         out = np.zeros(m, np.uint8)

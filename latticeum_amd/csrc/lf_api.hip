@@ -2116,6 +2116,8 @@ const uint64_t *lf_ccs_c_device(const lf_ccs *M) { return M ? M->c_dev : nullptr
 
 int lf_ccs_is_scalar(const lf_ccs *M) { return M && M->dev.sval ? 1 : 0; }
 
+int lf_ccs_is_reordered(const lf_ccs *M) { return M && M->dev.vh && M->dev.vc ? 1 : 0; }
+
 int lf_ccs_row_live(const lf_ccs *M, int j, uint8_t *out) {
   if (!M || !out || j < 0 || j >= M->dev.t) return LF_ERR_INVALID_ARG;
   std::copy(M->live.begin() + (size_t)j * M->dev.m, M->live.begin() + (size_t)(j + 1) * M->dev.m, out);
@@ -2156,8 +2158,16 @@ int lf_ccs_set_structure(lf_ctx *c, lf_ccs *M, size_t l, int degree, int q, cons
   return LF_OK;
 }
 
-// the largest pair of reordered ring-valued entry copies lf_ccs_create keeps (CcsDev::vh / vc)
+// the largest pair of reordered ring-valued entry copies lf_ccs_create keeps (CcsDev::vh / vc):
+// LATTICEUM_AMD_CCS_REORDER_BYTES in decimal bytes (0: no copies), read on every call
 constexpr size_t CCS_REORDER_BYTES = (size_t)16 << 30;
+static size_t ccs_reorder_bytes() {
+  const char *e = getenv("LATTICEUM_AMD_CCS_REORDER_BYTES");
+  if (!e || !*e) return CCS_REORDER_BYTES;
+  char *end = nullptr;
+  const unsigned long long v = strtoull(e, &end, 10);
+  return *end ? CCS_REORDER_BYTES : (size_t)v;
+}
 
 int lf_ccs_create(lf_ctx *c, int d, int t, size_t m, size_t n, const uint64_t *row_ptr, const uint32_t *col,
                   const uint64_t *val, int repr, lf_ccs **out) {
@@ -2276,16 +2286,21 @@ int lf_ccs_create(lf_ctx *c, int d, int t, size_t m, size_t n, const uint64_t *r
   // ring-valued entries: copies in the row-merged and transposes' orders, so the
   // challenged pass and the Mz weights read their values sequentially instead of
   // gathering d words per entry through hidx / cidx (at the zkvm's shape 2 x 3.15 GB;
-  // above CCS_REORDER_BYTES the gathers stay)
-  if (!D.sval && nnz && 2 * nnz * d * 8 <= CCS_REORDER_BYTES) {
+  // above ccs_reorder_bytes() the gathers stay). The copies are optional: when one
+  // cannot be allocated, both are dropped and the products gather
+  if (!D.sval && nnz && 2 * nnz * d * 8 <= ccs_reorder_bytes()) {
     const uint32_t *ix[2] = {D.hidx, D.cidx};
-    const uint64_t **dst[2] = {&D.vh, &D.vc};
-    for (int q = 0; q < 2; q++) {
-      LF_HIP(c, hipMalloc(&p, nnz * d * 8));
-      M->bufs.push_back(p);
-      LF_HIP(c, lfk::gather_entries(D.val, ix[q], nnz, d, (uint64_t *)p, c->cur));
-      *dst[q] = (const uint64_t *)p;
+    void *cp[2] = {nullptr, nullptr};
+    if (hipMalloc(&cp[0], nnz * d * 8) != hipSuccess || hipMalloc(&cp[1], nnz * d * 8) != hipSuccess) {
+      (void)hipGetLastError();  // clear it: not this call's failure
+      if (cp[0]) (void)hipFree(cp[0]);
+      cp[0] = cp[1] = nullptr;
     }
+    for (int q = 0; q < 2 && cp[0]; q++) M->bufs.push_back(cp[q]);
+    for (int q = 0; q < 2 && cp[0]; q++)
+      LF_HIP(c, lfk::gather_entries(D.val, ix[q], nnz, d, (uint64_t *)cp[q], c->cur));
+    D.vh = (const uint64_t *)cp[0];
+    D.vc = (const uint64_t *)cp[1];
   }
   LF_HIP(c, hipStreamSynchronize(c->cur));  // the host vectors go out of scope
   *out = M.release();

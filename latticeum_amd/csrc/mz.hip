@@ -219,7 +219,10 @@ __device__ __forceinline__ void zc_products(const v4i *A, const v4i *B, v4i *acc
 // [jl][c][24]; then one pass of whole 192-byte (j, c) elements out (16 consecutive
 // columns: 3 KiB contiguous per j).
 // SK (3 nz < 64, one K chunk with a zero tail: |acc_t| <= 3 nz 8 128^2 < 2^31 / 257): the
-// weights pair up in 32 bits first, W_m = acc_2m + 2^8 acc_2m+1, halving the 64-bit work
+// weights pair up in 32 bits first, W_m = acc_2m + 2^8 acc_2m+1, halving the 64-bit work.
+// The i32 accumulators hold kcn <= ZC_KCN_MAX = 255 chunks (|acc_t| <= kcn 2^23 < 2^31:
+// nz <= 5440); zcomb() runs k_zcomb<3> on the same scratch past that
+constexpr int ZC_KCN_MAX = 255;
 template <bool SK>
 __global__ void __launch_bounds__(64 * ZC_WAVES) k_zcomb_mfma(const v4i *af, const v4i *bf, int t, size_t n, int nrt,
                                                            int kcn, size_t nct, uint64_t *y) {
@@ -446,6 +449,11 @@ hipError_t zcomb(const CcsDev &M, const uint64_t *z, const uint64_t *zeta, int n
     const size_t nct = (M.n + 15) / 16;
     v4i *af = reinterpret_cast<v4i *>(scr + (size_t)M.t * nz * M.d), *bf = af + (size_t)ns * nrt * kcn * 512;
     hipLaunchKernelGGL(k_zeta_pows<3>, dim3(nblk((size_t)M.t * nz * ns, 256)), dim3(256), 0, st, zeta, nz, M.t, M.d, pw);
+    if (kcn > ZC_KCN_MAX) {  // more chunks than the i32 accumulators hold: the scalar form, pw | (unused) | y
+      hipLaunchKernelGGL(k_zcomb<3>, dim3(nblk((size_t)M.t * M.n * ns, 256)), dim3(256), 0, st, pw, z, nz, M.t, M.n,
+                         M.d, y);
+      return hipGetLastError();
+    }
     hipLaunchKernelGGL(k_zc_afrag, dim3(nblk((size_t)ns * nrt * kcn * 64, 256)), dim3(256), 0, st, pw, nz, M.t, nrt,
                        kcn, af);
     hipLaunchKernelGGL(k_zc_bfrag, dim3(nblk(nct * ns * kcn * 64, 512)), dim3(512), 0, st, z, nz, M.n, kcn, nct, bf);

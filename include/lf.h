@@ -41,6 +41,14 @@
  *   zkvm/src/zk_latticefold.rs:37-102 zk_latticefold_prove (fold())  -> lf_fold_prove
  *   zkvm/src/main.rs:305-344 initialize_accumulator's linearization  -> lf_linearize
  *   zkvm/src/zk_latticefold.rs:111-148 generate_verification_witness_vars -> lf_fold_replay
+ *   latticefold/src/arith.rs:78-105 CCS::check_relation            -> lf_dev_ccs_check_relation
+ *   zkvm/src/constraints.rs:1833-1871 check_relation_debug (zkvm/src/main.rs:171-172)
+ *                                                              -> lf_dev_ccs_check_relation, then
+ *                                                                 lf_dev_ccs_row_evals on the row
+ *   stark-rings/crates/ring/src/traits.rs:23-34 linf_norm (signed representatives,
+ *       balanced_decomposition/convertible_ring.rs:59-66)      -> lf_dev_linf_norm
+ *   the LCCCS / CCCS relations of an (instance, witness) pair  -> lf_lcccs_check / lf_cccs_check
+ *       (no single reference function: see their declaration)
  *   zkvm/src/main.rs:121-219  the proving loop, sharded over GPUs (SURVEY.md 8(b)
  *       lf_fold_reduce_allranks; no reference analogue: rayon only)
  *                                                              -> lf_comm_*, lf_dev_fold_step_sharded,
@@ -90,7 +98,8 @@ enum lf_status {
   LF_ERR_OUT_OF_MEMORY = 10,
   LF_ERR_COMM = 11,                   /* RCCL error (see lf_ctx_last_error) */
   LF_ERR_VERIFICATION = 12,           /* lf_fold_verify rejected the proof (which check: lf_verify_check) */
-  LF_ERR_UNSUPPORTED_CCS = 13         /* lf_prover_create: a multiset names the eq(beta) MLE (see lf_ctx_last_error) */
+  LF_ERR_UNSUPPORTED_CCS = 13,        /* lf_prover_create: a multiset names the eq(beta) MLE (see lf_ctx_last_error) */
+  LF_ERR_NOT_SATISFIED = 14           /* CSError::NotSatisfied(row) (lf_dev_ccs_check_relation) */
 };
 enum lf_repr { LF_REPR_CANONICAL = 0, LF_REPR_MONTGOMERY = 1 };
 
@@ -490,6 +499,24 @@ size_t lf_ccs_weights_len(const lf_ccs *M);
 int lf_dev_mz_weights(lf_ctx *ctx, const lf_ccs *M, int nv, const uint64_t *eq, uint64_t *w);
 int lf_dev_mz_dots(lf_ctx *ctx, const lf_ccs *M, const uint64_t *w, const uint64_t *z, int nz, uint64_t *out);
 
+/* ------------------------------------------------------------ relation checks (the reference's `debug` feature)
+ * CCS::check_relation (latticefold/src/arith.rs:78-105) for nz vectors z [nz][n][d] (device,
+ * canonical): sum_i c_i (.) prod_(j in S_i) (M_j z) = 0 on every row, in one fused pass over
+ * the entries of the matrices the multisets name (no M_j z is materialised; an empty
+ * multiset's product is ONE). first_bad[nz] (host): the smallest unsatisfied row of each z,
+ * or -1. resid (device, [nz][m][d], may be NULL): the residual itself. LF_OK if every z
+ * satisfies, LF_ERR_NOT_SATISFIED otherwise (first_bad is filled either way). Needs
+ * lf_ccs_set_structure (else LF_ERR_INVALID_ARG + lf_ctx_last_error). Synchronises the stream.
+ * check_relation_debug (zkvm/src/constraints.rs:1833-1871) is this call followed by
+ * lf_dev_ccs_row_evals on the reported row. */
+int lf_dev_ccs_check_relation(lf_ctx *ctx, const lf_ccs *M, const uint64_t *z, int nz, uint64_t *resid,
+                              int64_t *first_bad);
+/* out [t][d] (device) = (M_j z)[row] for every matrix j; z: one vector [n][d] (device) */
+int lf_dev_ccs_row_evals(lf_ctx *ctx, const lf_ccs *M, const uint64_t *z, size_t row, uint64_t *out);
+/* linf norm of n canonical words on the device, max min(x, p - x) -- linf_norm on signed
+ * representatives (stark-rings ring/src/traits.rs:23-34) -> *norm (host); synchronises */
+int lf_dev_linf_norm(lf_ctx *ctx, const uint64_t *x, size_t n, uint64_t *norm);
+
 /* ------------------------------------------------------------ width-8 Poseidon2 commitments
  * zkvm/src/commitments.rs:192-340, over Poseidon2Goldilocks<8> (poseidon2.rs:31-49;
  * external constants crypto_consts.rs:9-96; internal diagonal = Plonky3
@@ -651,6 +678,32 @@ int lf_linearize(lf_prover *prover, const uint64_t *cm, const uint64_t *x_ccs, c
 int lf_fold_prove(lf_prover *prover, const lf_lcccs *acc, const lf_witness *w_acc, const uint64_t *cm_i,
                   const uint64_t *x_ccs, const lf_witness *w_i, lf_lcccs_mut *out, const lf_witness *w_out,
                   lf_lfproof_mut *proof, int repr);
+/* Does this witness open this instance? The reference has no single function for the
+ * LCCCS relation; it is assembled here from Witness::commit (arith.rs:357: cm = A f),
+ * Witness::get_fhat evaluated at r (v), compute_u (linearization/utils.rs:24-29: u_j =
+ * MLE(M_j z)(r)) on get_z_vector's z = x_w || h || w_ccs (arith.rs:411-420), the
+ * witness's own three forms (Witness::from_f, arith.rs:299-313) and within_bound
+ * (arith.rs:372, dead code there, with its TODO of signed representatives done:
+ * lf_dev_linf_norm). The bound is the caller's: the right one depends on the
+ * parameter set (0: no norm check).
+ * LF_OK, or LF_ERR_VERIFICATION with the FIRST failed check in the enum's order in
+ * *failed. *norm (may be NULL) receives linf(f_coeff). repr describes the host buffers;
+ * the witness is device memory, canonical. lf_cccs_check: the CCCS (cm, x_ccs) with
+ * z = x_ccs || 1 || w_ccs; *row (may be NULL) receives LF_REL_CCS's first unsatisfied row. */
+enum lf_relation_check {
+  LF_REL_OK = 0,
+  LF_REL_WITNESS_F = 1, /* f != CRT(f_coeff) */
+  LF_REL_WITNESS_W = 2, /* w_ccs != Witness::from_f(f).w_ccs (gadget recomposition) */
+  LF_REL_NORM = 3,      /* bound != 0 and linf(f_coeff) >= bound */
+  LF_REL_CM = 4,        /* cm != A f */
+  LF_REL_V = 5,         /* v != f_hat(r) */
+  LF_REL_U = 6,         /* u_j != MLE(M_j z)(r), z = x_w || h || w_ccs (arith.rs:411-420) */
+  LF_REL_CCS = 7        /* CCS::check_relation(x_ccs || 1 || w_ccs) fails; row in *row */
+};
+int lf_lcccs_check(lf_prover *prover, const lf_lcccs *acc, const lf_witness *w, uint64_t bound, uint64_t *norm,
+                   int *failed, int repr);
+int lf_cccs_check(lf_prover *prover, const uint64_t *cm, const uint64_t *x_ccs, const lf_witness *w, uint64_t bound,
+                  uint64_t *norm, int *failed, int64_t *row, int repr);
 /* the halves of the device fold step that fold() interleaves with its sumchecks:
  *   lf_dev_decompose_commit: decompose_witness + commit_witnesses of both sides
  *     (y_0 included), inputs acc_f_coeff, acc_cm, f_coeff and cm (the linearized instance)

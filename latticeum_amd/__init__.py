@@ -418,6 +418,13 @@ class Context:
     def dev_modp_sum(self, inp, nparts: int, length: int, out):
         self.check(self.lib.lf_dev_modp_sum(self.h, _dptr(inp), nparts, length, _dptr(out)))
 
+    def dev_linf_norm(self, t) -> int:
+        """linf norm of a device tensor of canonical words on their signed representatives,
+        max min(x, p - x) (lf_dev_linf_norm); synchronises"""
+        out = C.c_uint64(0)
+        self.check(self.lib.lf_dev_linf_norm(self.h, _dptr(t), t.numel(), C.byref(out)))
+        return out.value
+
 
 class Communicator:
     """lf_comm: an RCCL communicator of one rank, for the accumulator exchange
@@ -555,6 +562,33 @@ class CCSMatrices:
     def mz_evaluate(self, z, nz: int, nv: int, point, out):
         self.ctx.check(self.lib.lf_dev_mz_evaluate(self.ctx.h, self.h, _dptr(z), nz, nv, _dptr(point), _dptr(out)))
 
+    def set_structure(self, l: int, degree: int, c, S, repr: int = REPR_CANONICAL):
+        """the CCS's l, degree, c (q NTT elements) and multisets S (lf_ccs_set_structure)"""
+        c = _u64(c)
+        off = np.zeros(len(S) + 1, np.int32)
+        off[1:] = np.cumsum([len(x) for x in S])
+        idx = np.array([j for x in S for j in x] or [0], np.int32)
+        self.ctx.check(self.lib.lf_ccs_set_structure(self.ctx.h, self.h, l, degree, len(S), _ptr(c), _ptr(off),
+                                                     _ptr(idx), repr))
+
+    def check_relation(self, z, nz: int = 1, resid=None) -> list:
+        """CCS::check_relation of nz device vectors z [nz][n][d] (lf_dev_ccs_check_relation):
+        the first unsatisfied row of each, or -1; resid (device, [nz][m][d], optional)
+        receives the residual. The rows are the result: an unsatisfied z does not raise
+        (last_status then holds LF_ERR_NOT_SATISFIED, else 0)."""
+        fb = (C.c_int64 * nz)()
+        rc = self.lib.lf_dev_ccs_check_relation(self.ctx.h, self.h, _dptr(z), nz,
+                                                _dptr(resid) if resid is not None else None, fb)
+        if rc != ERR_NOT_SATISFIED:
+            self.ctx.check(rc)
+        self.last_status = rc
+        return list(fb)
+
+    def row_evals(self, z, row: int, out):
+        """out [t][d] = (M_j z)[row] for every matrix (lf_dev_ccs_row_evals): the values
+        check_relation_debug prints for a failing row"""
+        self.ctx.check(self.lib.lf_dev_ccs_row_evals(self.ctx.h, self.h, _dptr(z), row, _dptr(out)))
+
     def __del__(self):
         try:
             if self.h:
@@ -677,6 +711,40 @@ class Prover:
         out["x_w"] = out["x_w"][:l * d]
         return out, sc
 
+    def _relation_result(self, rc: int, failed: int, row: int, norm: int) -> int:
+        if rc == 12:
+            raise RelationError(failed, row if failed == REL_CCS else None)
+        if rc:
+            raise LfError(rc, self.lib.lf_prover_last_error(self.h).decode() or self.lib.lf_status_string(rc).decode())
+        return norm
+
+    def check_lcccs(self, acc: dict, w: dict, bound: int = 0, repr: int = REPR_CANONICAL) -> int:
+        """does the device witness w = {w_ccs, f, f_coeff} open the LCCCS acc = {r, v, cm, u,
+        x_w, h} (lf_lcccs_check)? Returns linf(f_coeff); RelationError names the first failed
+        check. bound != 0: the norm must be below it."""
+        from ._lib import LfLcccs, LfRingSlice, LfWitness
+        d = self.d
+        keep = {k: _u64(v) for k, v in acc.items()}
+        sl = lambda a: LfRingSlice(a.ctypes.data if a.size else None, a.size // d)
+        A = LfLcccs(d, sl(keep["r"]), sl(keep["v"]), sl(keep["cm"]), sl(keep["u"]), sl(keep["x_w"]),
+                    keep["h"].ctypes.data)
+        wi = LfWitness(_dptr(w["w_ccs"]), _dptr(w["f"]), _dptr(w["f_coeff"]))
+        norm, failed = C.c_uint64(0), C.c_int(0)
+        rc = self.lib.lf_lcccs_check(self.h, C.byref(A), C.byref(wi), bound, C.byref(norm), C.byref(failed), repr)
+        return self._relation_result(rc, failed.value, -1, norm.value)
+
+    def check_cccs(self, cm, x_ccs, w: dict, bound: int = 0, repr: int = REPR_CANONICAL) -> int:
+        """does the device witness w open the CCCS (cm, x_ccs) and satisfy the CCS
+        (lf_cccs_check)? Returns linf(f_coeff); RelationError names the first failed check
+        and, for the CCS relation, the first unsatisfied row."""
+        from ._lib import LfWitness
+        cm, xc = _u64(cm), (_u64(x_ccs) if self.l else np.zeros(1, np.uint64))
+        wi = LfWitness(_dptr(w["w_ccs"]), _dptr(w["f"]), _dptr(w["f_coeff"]))
+        norm, failed, row = C.c_uint64(0), C.c_int(0), C.c_int64(-1)
+        rc = self.lib.lf_cccs_check(self.h, cm.ctypes.data, xc.ctypes.data, C.byref(wi), bound, C.byref(norm),
+                                    C.byref(failed), C.byref(row), repr)
+        return self._relation_result(rc, failed.value, row.value, norm.value)
+
     def __del__(self):
         try:
             if self.h:
@@ -751,6 +819,23 @@ class VerificationError(LfError):
     def __init__(self, check: int):
         super().__init__(12, VERIFY_CHECKS.get(check, str(check)))
         self.check = check
+
+
+ERR_NOT_SATISFIED = 14  # lf.h LF_ERR_NOT_SATISFIED
+REL_WITNESS_F, REL_WITNESS_W, REL_NORM, REL_CM, REL_V, REL_U, REL_CCS = range(1, 8)  # lf.h lf_relation_check
+RELATION_CHECKS = {REL_WITNESS_F: "f != CRT(f_coeff)", REL_WITNESS_W: "w_ccs != from_f(f).w_ccs",
+                   REL_NORM: "linf(f_coeff) >= bound", REL_CM: "cm != A f", REL_V: "v != f_hat(r)",
+                   REL_U: "u != MLE(M z)(r)", REL_CCS: "the CCS relation is not satisfied"}
+
+
+class RelationError(LfError):
+    """Prover.check_lcccs / check_cccs: .check is the first failed lf_relation_check, .row
+    the first unsatisfied row when that is the CCS relation (else None)"""
+
+    def __init__(self, check: int, row: int | None = None):
+        what = RELATION_CHECKS.get(check, str(check))
+        super().__init__(12, what if row is None else f"{what} (row {row})")
+        self.check, self.row = check, row
 
 
 def fold_verify(params: LfParams, t: int, m: int, l: int, degree: int, c, S, kappa: int, acc: dict, cm_i, x_ccs,
@@ -997,5 +1082,5 @@ __all__ = ["Context", "AjtaiCommitmentScheme", "Communicator", "Comb", "CCSMatri
            "LfParams", "LfFoldStepBufs", "merkle_nodes_len", "merkle_depth", "hash_w8", "vm_mem_comm",
            "LfError", "goldilocks_dp", "short_challenge", "hash_iter", "hash_iter_states", "acc_comm",
            "ivc_step_comm", "state_i_comm", "vm_regs_comm", "vm_mem_ops_vec_comm", "fold_verify",
-           "VerificationError", "P", "REPR_CANONICAL",
+           "VerificationError", "RelationError", "P", "REPR_CANONICAL",
            "REPR_MONTGOMERY", "load"]

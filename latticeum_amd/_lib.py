@@ -214,6 +214,12 @@ SIGNATURES = {
     "lf_ccs_weights_len": (SZ, [VP]),
     "lf_dev_mz_weights": (I, [VP, VP, I, VP, VP]),
     "lf_dev_mz_dots": (I, [VP, VP, VP, VP, I, VP]),
+    "lf_dev_ccs_check_relation": (I, [VP, VP, VP, I, VP, C.POINTER(C.c_int64)]),
+    "lf_dev_ccs_row_evals": (I, [VP, VP, VP, SZ, VP]),
+    "lf_dev_linf_norm": (I, [VP, VP, SZ, C.POINTER(U64)]),
+    "lf_lcccs_check": (I, [VP, C.POINTER(LfLcccs), C.POINTER(LfWitness), U64, C.POINTER(U64), C.POINTER(I), I]),
+    "lf_cccs_check": (I, [VP, VP, VP, C.POINTER(LfWitness), U64, C.POINTER(U64), C.POINTER(I),
+                          C.POINTER(C.c_int64), I]),
     "lf_dev_fhat_evaluate_eq": (I, [VP, I, VP, SZ, SZ, I, I, VP, VP]),
     "lf_dev_mle_fix_first": (I, [VP, I, VP, SZ, I, I, VP, VP, SZ]),
     "lf_dev_mle_evaluate": (I, [VP, I, VP, I, I, VP, VP]),

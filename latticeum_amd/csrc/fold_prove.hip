@@ -57,6 +57,7 @@ struct lf_prover {
   // eq(r_0) and one point's Mz weights M_j^T eq (shared by the sides evaluated there)
   uint64_t *eq0 = nullptr, *mzw = nullptr;
   uint64_t *lev = nullptr;  // the live Mz MLEs at r_lin (the linearization sumcheck's final values)
+  uint64_t *chk = nullptr;  // lf_lcccs_check / lf_cccs_check: the compare kernel's result words
   std::string err;
   // every value the last lf_fold_prove sampled from its transcript, in order
   // (lf_fold_prove_vars replays the proof on them instead of a second sponge)
@@ -281,6 +282,58 @@ int bad(lf_prover *P, int code, const char *msg) {
   return code;
 }
 
+// restores the calling thread's device on scope exit
+struct OnDevice {
+  int prev = -1, dev;
+  explicit OnDevice(int device) : dev(device) {
+    if (hipGetDevice(&prev) == hipSuccess && prev != dev) (void)hipSetDevice(dev);
+  }
+  ~OnDevice() {
+    if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
+  }
+};
+
+// The checks a witness answers for on its own and against its commitment, shared by
+// lf_lcccs_check and lf_cccs_check: LF_REL_WITNESS_F, _W (Witness::from_f of f against
+// f_coeff and w_ccs: f = CRT(f_coeff) iff ICRT(f) = f_coeff), LF_REL_NORM and LF_REL_CM
+// (Witness::commit, arith.rs:357). cm: host, canonical. *failed = the first that fails
+// (LF_REL_OK: none); the return value is R.rc
+int witness_checks(lf_prover *P, Run &R, const lf_witness *w, const uint64_t *cm, uint64_t bound, uint64_t *norm,
+                   int *failed) {
+  lf_ctx *C = P->ctx;
+  const int d = P->d;
+  const size_t N = P->N, W = P->W, kd = P->kappa * d;
+  *failed = LF_REL_OK;
+  uint64_t *fc = P->fkc[0], *wc = P->wk[0];  // N and W elements of the decomposition's planes
+  R.check(lf_dev_witness_from_f(C, &P->pr, w->f, N, fc, wc), "Witness::from_f");
+  if (R.rc) return R.rc;
+  R.hip(lfk::first_diff(fc, w->f_coeff, N * d, P->chk, R.st), "compare f_coeff");
+  R.hip(lfk::first_diff(wc, w->w_ccs, W * d, P->chk + 1, R.st), "compare w_ccs");
+  uint64_t diff[2] = {0, 0}, nm = 0;
+  R.d2h(diff, P->chk, 2);
+  R.check(lf_dev_linf_norm(C, w->f_coeff, N * d, &nm), "linf norm");
+  if (R.rc) return R.rc;
+  if (norm) *norm = nm;
+  if (diff[0] != ~0ull) return *failed = LF_REL_WITNESS_F, R.rc;
+  if (diff[1] != ~0ull) return *failed = LF_REL_WITNESS_W, R.rc;
+  if (bound && nm >= bound) return *failed = LF_REL_NORM, R.rc;
+  const uint64_t *vecs[1] = {w->f};
+  R.check(lf_dev_ajtai_commit(C, P->aj, vecs, 1, P->cmd[0]), "commit");
+  std::vector<uint64_t> got(kd);
+  R.d2h(got.data(), P->cmd[0], kd);
+  if (R.rc) return R.rc;
+  if (memcmp(got.data(), cm, kd * 8)) *failed = LF_REL_CM;
+  return R.rc;
+}
+
+// z = x || h || w_ccs in P->z (get_z_vector, arith.rs:411-420); x: l host elements, h: one
+void assemble_z(lf_prover *P, Run &R, const uint64_t *x, const uint64_t *h, const lf_witness *w) {
+  const int d = P->d;
+  R.h2d(P->z, x, P->l * d);
+  R.h2d(P->z + P->l * d, h, d);
+  R.d2d(P->z + (P->l + 1) * d, w->w_ccs, P->W * d);
+}
+
 }  // namespace
 
 extern "C" {
@@ -421,7 +474,7 @@ int lf_prover_create(lf_ctx *ctx, const lf_ajtai *aj, const lf_params *pr, const
       {&P->theta, 2 * K * tau * d}, {&P->eta, 2 * K * t * d}, {&P->rho, 2 * K * d}, {&P->rhoc, 2 * K * d},
       {&P->cm0, kd}, {&P->u0, (size_t)t * d}, {&P->x0, (l + 1) * d}, {&P->v0, tau * d}, {&P->r0, (size_t)P->s * d},
       {&P->eq0, nn * d}, {&P->mzw, lf_ccs_weights_len(ccs)}, {&P->lev, (size_t)t * d},
-      {reinterpret_cast<uint64_t **>(&P->act), (P->act_host.size() + 1) / 2}};
+      {&P->chk, 2}, {reinterpret_cast<uint64_t **>(&P->act), (P->act_host.size() + 1) / 2}};
   size_t total = 0;
   for (auto &x : parts) total += (x.elems + 31) / 32 * 32;  // 256-B aligned parts
   int prev = -1;
@@ -923,6 +976,80 @@ size_t lf_prover_samples(const lf_prover *P, uint64_t *out, size_t cap) {
   if (!P) return 0;
   if (out) memcpy(out, P->samples.data(), (cap < P->samples.size() ? cap : P->samples.size()) * 8);
   return P->samples.size();
+}
+
+// ---------------------------------------------------------------- does this witness open this instance?
+int lf_lcccs_check(lf_prover *P, const lf_lcccs *acc, const lf_witness *w, uint64_t bound, uint64_t *norm, int *failed,
+                   int repr) {
+  if (!P || !acc || !w || !failed) return LF_ERR_INVALID_ARG;
+  *failed = LF_REL_OK;
+  if (repr != LF_REPR_CANONICAL && repr != LF_REPR_MONTGOMERY) return bad(P, LF_ERR_INVALID_ARG, "repr");
+  const int d = P->d, tau = P->tau, s = P->s, t = P->t;
+  const size_t l = P->l, kd = P->kappa * d;
+  if (acc->d != d || acc->r.n != (size_t)s || acc->v.n != (size_t)tau || acc->cm.n != P->kappa || acc->u.n != (size_t)t ||
+      acc->x_w.n != l || !acc->h)
+    return bad(P, LF_ERR_INCORRECT_LENGTH, "LCCCS sizes (r: s, v: tau, cm: kappa, u: t, x_w: l)");
+  if (!w->f || !w->f_coeff || !w->w_ccs) return bad(P, LF_ERR_INVALID_ARG, "missing witness buffer");
+  auto canon = [&](const uint64_t *src, size_t elems) {
+    std::vector<uint64_t> v(src, src + elems);
+    if (repr == LF_REPR_MONTGOMERY)
+      for (auto &x : v) x = gl::from_mont(x);
+    return v;
+  };
+  const std::vector<uint64_t> ar = canon(acc->r.elems, (size_t)s * d), av = canon(acc->v.elems, (size_t)tau * d),
+                              acm = canon(acc->cm.elems, kd), au = canon(acc->u.elems, (size_t)t * d),
+                              axw = canon(acc->x_w.elems, l * d), ah = canon(acc->h, d);
+  lf_ctx *C = P->ctx;
+  OnDevice dg(P->device);
+  Run R{P, nullptr, (hipStream_t)lf_ctx_get_stream(C)};
+  if (witness_checks(P, R, w, acm.data(), bound, norm, failed)) return R.rc;
+  if (*failed) return LF_ERR_VERIFICATION;
+  // v = f_hat(r) and u_j = MLE(M_j z)(r) (compute_u, linearization/utils.rs:24-29)
+  std::vector<uint64_t> got((size_t)std::max(tau, t) * d);
+  R.h2d(P->pt, ar.data(), (size_t)s * d);
+  R.check(lf_dev_fhat_evaluate(C, d, w->f_coeff, P->N, 0, 1, s, P->pt, P->val), "v");
+  R.d2h(got.data(), P->val, (size_t)tau * d);
+  if (R.rc) return R.rc;
+  if (memcmp(got.data(), av.data(), (size_t)tau * d * 8)) return *failed = LF_REL_V, LF_ERR_VERIFICATION;
+  assemble_z(P, R, axw.data(), ah.data(), w);
+  R.check(lf_dev_mz_evaluate(C, P->ccs, P->z, 1, s, P->pt, P->us), "u");
+  R.d2h(got.data(), P->us, (size_t)t * d);
+  if (R.rc) return R.rc;
+  if (memcmp(got.data(), au.data(), (size_t)t * d * 8)) return *failed = LF_REL_U, LF_ERR_VERIFICATION;
+  return LF_OK;
+}
+
+int lf_cccs_check(lf_prover *P, const uint64_t *cm, const uint64_t *x_ccs, const lf_witness *w, uint64_t bound,
+                  uint64_t *norm, int *failed, int64_t *row, int repr) {
+  if (!P || !cm || (!x_ccs && P->l) || !w || !failed) return LF_ERR_INVALID_ARG;
+  *failed = LF_REL_OK;
+  if (row) *row = -1;
+  if (repr != LF_REPR_CANONICAL && repr != LF_REPR_MONTGOMERY) return bad(P, LF_ERR_INVALID_ARG, "repr");
+  if (!w->f || !w->f_coeff || !w->w_ccs) return bad(P, LF_ERR_INVALID_ARG, "missing witness buffer");
+  const int d = P->d;
+  const size_t l = P->l, kd = P->kappa * d;
+  std::vector<uint64_t> cmv(cm, cm + kd), xc(x_ccs ? x_ccs : cm, x_ccs ? x_ccs + l * d : cm);
+  if (repr == LF_REPR_MONTGOMERY) {
+    for (auto &x : cmv) x = gl::from_mont(x);
+    for (auto &x : xc) x = gl::from_mont(x);
+  }
+  lf_ctx *C = P->ctx;
+  OnDevice dg(P->device);
+  Run R{P, nullptr, (hipStream_t)lf_ctx_get_stream(C)};
+  if (witness_checks(P, R, w, cmv.data(), bound, norm, failed)) return R.rc;
+  if (*failed) return LF_ERR_VERIFICATION;
+  // CCS::check_relation of z = x_ccs || 1 || w_ccs (arith.rs:78-105)
+  std::vector<uint64_t> one(d, 0);
+  for (int i = 0; i < d; i += P->tb) one[i] = 1;
+  assemble_z(P, R, xc.data(), one.data(), w);
+  if (R.rc) return R.rc;
+  int64_t fb = -1;
+  const int rc = lf_dev_ccs_check_relation(C, P->ccs, P->z, 1, nullptr, &fb);
+  if (rc == LF_ERR_NOT_SATISFIED) {
+    if (row) *row = fb;
+    return *failed = LF_REL_CCS, LF_ERR_VERIFICATION;
+  }
+  return R.check(rc, "CCS relation");
 }
 
 }  // extern "C"

@@ -381,4 +381,17 @@ size_t mz_dots_partial_elems(const CcsDev &M, int nz);
 hipError_t mz_evaluate(const CcsDev &M, const uint64_t *z, int nz, int nv, const uint64_t *point, uint64_t *out,
                        uint64_t *scratch, hipStream_t st);
 
+// ---------------------------------------------------------------- relation checks (relation.hip)
+// CCS::check_relation of nz vectors z [nz][n][d]: first_bad [nz] (device) = the smallest row r
+// with sum_i c_i (.) prod_(j in S_i) (M_j z)[r] != 0, or all-ones; resid (device, [nz][m][d],
+// may be null) = that sum. c [q][d], S_off [q + 1], S_idx: device. No M_j z is materialised
+hipError_t ccs_relation(const CcsDev &M, const uint64_t *z, int nz, const uint64_t *c, int q, const int *S_off,
+                        const int *S_idx, uint64_t *resid, uint64_t *first_bad, hipStream_t st);
+// out [t][d] = (M_j z)[row]
+hipError_t ccs_row_evals(const CcsDev &M, const uint64_t *z, size_t row, uint64_t *out, hipStream_t st);
+// *out (device) = max over n canonical words of min(x, p - x)
+hipError_t linf_norm(const uint64_t *x, size_t n, uint64_t *out, hipStream_t st);
+// *out (device) = the smallest i with a[i] != b[i], or all-ones
+hipError_t first_diff(const uint64_t *a, const uint64_t *b, size_t n, uint64_t *out, hipStream_t st);
+
 }  // namespace lfk

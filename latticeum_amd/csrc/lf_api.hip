@@ -77,6 +77,8 @@ struct lf_ctx {
   size_t ptrs_elems = 0;
   int *sel = nullptr;           // lf_dev_mz_mles_sel: the selected matrices
   size_t sel_elems = 0;
+  uint64_t *rel = nullptr;      // relation checks: the first unsatisfied row per z, the norm
+  size_t rel_elems = 0;
   uint64_t *hmsg = nullptr;     // pinned host staging of the sumcheck round messages
   size_t hmsg_elems = 0;
   lfk::FoldRows fold_rows{};    // a step without f_k buffers: where its 2K planes sit in the operand rows
@@ -127,6 +129,8 @@ struct lf_ccs {
   std::vector<uint8_t> live;   // [t][m]: row r of M_j holds an entry
   uint64_t *c_dev = nullptr;   // in bufs
   size_t c_dev_elems = 0;
+  int *S_dev = nullptr;        // S_off [q + 1] then S_idx (the relation kernel's copy), in bufs
+  size_t S_dev_elems = 0;
   ~lf_ccs() {  // every device buffer, also on a failed lf_ccs_create
     DevGuardBase g(device);
     for (void *p : bufs) (void)hipFree(p);
@@ -971,6 +975,7 @@ const char *lf_status_string(int s) {
     case LF_ERR_COMM: return "RCCL communicator error";
     case LF_ERR_VERIFICATION: return "the folding proof does not verify";
     case LF_ERR_UNSUPPORTED_CCS: return "unsupported CCS structure";
+    case LF_ERR_NOT_SATISFIED: return "the CCS relation is not satisfied";
   }
   return "unknown status";
 }
@@ -1030,6 +1035,7 @@ void lf_ctx_destroy(lf_ctx *c) {
   if (c->sc) (void)hipFree(c->sc);
   if (c->ptrs) (void)hipFree(c->ptrs);
   if (c->sel) (void)hipFree(c->sel);
+  if (c->rel) (void)hipFree(c->rel);
   if (c->hmsg) (void)hipHostFree(c->hmsg);
   if (c->join) (void)hipEventDestroy(c->join);
   if (c->cjoin) (void)hipEventDestroy(c->cjoin);
@@ -2153,6 +2159,18 @@ int lf_ccs_set_structure(lf_ctx *c, lf_ccs *M, size_t l, int degree, int q, cons
     M->c_dev_elems = (size_t)q * d;
   }
   LF_HIP(c, hipMemcpyAsync(M->c_dev, M->c.data(), (size_t)q * d * 8, hipMemcpyHostToDevice, c->cur));
+  const size_t s_elems = (size_t)q + 1 + M->S_idx.size();
+  if (!M->S_dev || M->S_dev_elems < s_elems) {
+    void *p = nullptr;
+    LF_HIP(c, hipMalloc(&p, s_elems * sizeof(int)));
+    M->bufs.push_back(p);
+    M->S_dev = (int *)p;
+    M->S_dev_elems = s_elems;
+  }
+  LF_HIP(c, hipMemcpyAsync(M->S_dev, M->S_off.data(), ((size_t)q + 1) * sizeof(int), hipMemcpyHostToDevice, c->cur));
+  if (!M->S_idx.empty())
+    LF_HIP(c, hipMemcpyAsync(M->S_dev + q + 1, M->S_idx.data(), M->S_idx.size() * sizeof(int), hipMemcpyHostToDevice,
+                             c->cur));
   LF_HIP(c, hipStreamSynchronize(c->cur));
   M->structured = true;
   return LF_OK;
@@ -2385,6 +2403,49 @@ int lf_dev_mz_dots(lf_ctx *c, const lf_ccs *M, const uint64_t *w, const uint64_t
 }
 
 size_t lf_ccs_weights_len(const lf_ccs *M) { return M ? (size_t)M->dev.t * M->dev.n * M->dev.d : 0; }
+
+// ---------------------------------------------------------------- relation checks
+int lf_dev_ccs_check_relation(lf_ctx *c, const lf_ccs *M, const uint64_t *z, int nz, uint64_t *resid,
+                              int64_t *first_bad) {
+  if (!c || !z || !first_bad) return LF_ERR_INVALID_ARG;
+  DevGuard g(c);
+  if (!M || nz < 1 || nz > 65535) return fail(c, LF_ERR_INVALID_ARG, "CCS relation: null matrices or nz outside 1..65535");
+  if (M->device != c->device) return fail(c, LF_ERR_INVALID_ARG, "CCS matrices live on another device");
+  if (!M->structured) return fail(c, LF_ERR_INVALID_ARG, "CCS relation: lf_ccs_set_structure first (c and the multisets)");
+  const int q = (int)M->S_off.size() - 1;
+  LF_TRY(grow(c, c->rel, c->rel_elems, (size_t)nz));
+  LF_HIP(c, lfk::ccs_relation(M->dev, z, nz, M->c_dev, q, M->S_dev, M->S_dev + q + 1, resid, c->rel, c->cur));
+  std::vector<uint64_t> fb(nz);
+  LF_HIP(c, hipMemcpyAsync(fb.data(), c->rel, (size_t)nz * 8, hipMemcpyDeviceToHost, c->cur));
+  LF_HIP(c, hipStreamSynchronize(c->cur));
+  bool ok = true;
+  for (int i = 0; i < nz; i++) {
+    first_bad[i] = fb[i] == ~0ull ? -1 : (int64_t)fb[i];
+    ok &= first_bad[i] < 0;
+  }
+  return ok ? LF_OK : LF_ERR_NOT_SATISFIED;
+}
+
+int lf_dev_ccs_row_evals(lf_ctx *c, const lf_ccs *M, const uint64_t *z, size_t row, uint64_t *out) {
+  if (!c || !z || !out) return LF_ERR_INVALID_ARG;
+  DevGuard g(c);
+  if (!M) return fail(c, LF_ERR_INVALID_ARG, "CCS row values: null matrices");
+  if (M->device != c->device) return fail(c, LF_ERR_INVALID_ARG, "CCS matrices live on another device");
+  if (row >= M->dev.m) return fail(c, LF_ERR_INVALID_ARG, "CCS row values: row out of range");
+  LF_HIP(c, lfk::ccs_row_evals(M->dev, z, row, out, c->cur));
+  return LF_OK;
+}
+
+int lf_dev_linf_norm(lf_ctx *c, const uint64_t *x, size_t n, uint64_t *norm) {
+  if (!c || !norm || (n && !x)) return LF_ERR_INVALID_ARG;
+  DevGuard g(c);
+  if ((uintptr_t)x & 7) return fail(c, LF_ERR_INVALID_ARG, "linf norm: the words must be 8-byte aligned");
+  LF_TRY(grow(c, c->rel, c->rel_elems, (size_t)1));
+  LF_HIP(c, lfk::linf_norm(x, n, c->rel, c->cur));
+  LF_HIP(c, hipMemcpyAsync(norm, c->rel, 8, hipMemcpyDeviceToHost, c->cur));
+  LF_HIP(c, hipStreamSynchronize(c->cur));
+  return LF_OK;
+}
 
 // ---------------------------------------------------------------- width-8 Poseidon2 Merkle trees
 int lf_dev_poseidon2_w8_permute(lf_ctx *c, uint64_t *states, size_t n) {

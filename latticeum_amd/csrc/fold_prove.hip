@@ -20,9 +20,7 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/lf.h"
-#include "gl.hpp"
-#include "kernels.hpp"
+#include "api_internal.hpp"
 
 struct lf_prover {
   lf_ctx *ctx = nullptr;
@@ -90,21 +88,6 @@ namespace {
 // t blocks each, and the host starts absorbing after the first group
 constexpr int MZ_GROUP = 2;
 
-// the Fq3 = Fq[u]/(u^3 - 2^40) product of two base-ring elements (tb = 3), or the Fq one
-void base_mul(const uint64_t *a, const uint64_t *b, uint64_t *o, int tb) {
-  if (tb == 1) {
-    o[0] = gl::mul(a[0], b[0]);
-    return;
-  }
-  const uint64_t nr = 1ull << 40;
-  const uint64_t c0 = gl::add(gl::mul(a[0], b[0]), gl::mul(nr, gl::add(gl::mul(a[1], b[2]), gl::mul(a[2], b[1]))));
-  const uint64_t c1 = gl::add(gl::add(gl::mul(a[0], b[1]), gl::mul(a[1], b[0])), gl::mul(nr, gl::mul(a[2], b[2])));
-  const uint64_t c2 = gl::add(gl::add(gl::mul(a[0], b[2]), gl::mul(a[1], b[1])), gl::mul(a[2], b[0]));
-  o[0] = c0;
-  o[1] = c1;
-  o[2] = c2;
-}
-
 // From<BaseRing> = from_scalar: the base-ring element in every NTT slot
 void broadcast(const uint64_t *base, int tb, int d, uint64_t *out) {
   for (int i = 0; i < d; i++) out[i] = base[i % tb];
@@ -171,20 +154,9 @@ struct Run {
   void absorb_label(const char *label) {
     uint64_t v = 0;
     for (const char *p = label; *p; p++) v = gl::add(gl::mul(v, 256), (uint8_t)*p);
-    std::vector<uint64_t> e(P->d, 0);
-    for (int i = 0; i < P->d; i += P->tb) e[i] = v;
-    absorb(e.data(), 1);
+    absorb_scalar(T, v, P->d);
   }
-  // get_challenge (fiat_shamir.rs:69-86): three samples re-observed for Fq3;
-  // one sample re-observed for Fq (this project's convention for X^d + 1)
-  void challenge(uint64_t *out) {
-    if (P->tb == 3) {
-      lf_transcript_get_challenge(T, out);
-    } else {
-      out[0] = lf_transcript_sample(T);
-      lf_transcript_observe(T, out[0]);
-    }
-  }
+  void challenge(uint64_t *out) { sample_challenge(T, P->tb, out); }
   // get_challenges(n) mapped into NTT elements: [n][d]
   std::vector<uint64_t> challenges(size_t n) {
     std::vector<uint64_t> out(n * P->d);
@@ -784,7 +756,7 @@ int lf_fold_prove(lf_prover *P, const lf_lcccs *acc, const lf_witness *w_acc, co
       for (int j = 0; j < tau; j++) {
         broadcast(pw, tb, d, cf.data() + ((size_t)k * tau + j) * d);
         uint64_t nx[3];
-        base_mul(pw, a, nx, tb);
+        gl::base_mul(pw, a, nx, tb);
         memcpy(pw, nx, sizeof(pw));
       }
     }

@@ -226,6 +226,13 @@ LF_HD void fq3_mul(const uint64_t *a, const uint64_t *b, uint64_t *c) {
   c[1] = c1;
   c[2] = c2;
 }
+// the product of two base-ring elements of tb words: Fq3 (tb = 3) or Fq (tb = 1); o may alias a or b
+LF_HD void base_mul(const uint64_t *a, const uint64_t *b, uint64_t *o, int tb) {
+  if (tb == 3)
+    fq3_mul(a, b, o);
+  else
+    o[0] = mul(a[0], b[0]);
+}
 
 // ---- lazy 128-bit multiply-accumulate: acc = sum of a_i*b_i as
 // (lo:64, hi:64, top:32) -- reduce once at the end ----

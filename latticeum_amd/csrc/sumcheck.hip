@@ -458,7 +458,7 @@ __global__ void __launch_bounds__(RT) k_round_lin(const uint64_t *mles, size_t s
 //   p(X) = P eq(beta_0, X) q(X),  q(X) = sum_b E[b] sum_i c_i prod_(j in S_i) m_j(X, b)
 // q has one degree less than p, so NQ = degree values q(0 .. NQ-1) suffice; the
 // host extrapolates q(NQ) and multiplies in the eq factors (sumcheck_run_lin,
-// lf_api.hip). p(e) is the same field element either way, so the messages are
+// api_sumcheck.hip). p(e) is the same field element either way, so the messages are
 // the reference's (prover.rs:62-168 over linearization/utils.rs:63-104).
 //
 // A multiset's product c_i prod_f (a_f + d_f e) is formed in two groups in

@@ -390,6 +390,15 @@ def test_dev_fold_step_repeated_in_place(ctx):
     check_dev_fold_step(ctx, 1024, 37, 2, steps=3)
 
 
+def test_dev_fold_step_fused_then_fragmentless_scheme(ctx):
+    """a fused d = 1024 step, then on the same context and at the same N a scheme
+    with no MFMA fragments (kappa = 130 > 128): the second step folds its own
+    witness (NTT-form, from its f_k rows), never the first step's digits left in
+    the context's sign|magnitude scratch"""
+    check_dev_fold_step(ctx, 1024, 2, 2, steps=2)
+    check_dev_fold_step(ctx, 1024, 2, 130)
+
+
 @pytest.mark.parametrize("d,W", [(24, 3), (24, 17), (24, 70), (1024, 2), (1024, 37), (1024, 130)])
 @pytest.mark.parametrize("short", [True, False])
 def test_dev_fold_step_packed_planes(ctx, d, W, short):

@@ -18,7 +18,7 @@ import json
 import os
 import sys
 
-# every kernel a phase's HIP-event pair brackets (lf_api.hip fold_commit / fold_finish),
+# every kernel a phase's HIP-event pair brackets (api_step.hip fold_commit / fold_finish),
 # by base name; the primary kernel (launched once per phase record) comes first
 PHASE_KERNELS = {
     "decompose": ("k_decompose_fused", "k_decompose_phi72_w", "k_decompose_n4k_mx", "k_decompose_n4k_fused", "k_decompose_n4k",

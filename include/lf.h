@@ -322,7 +322,12 @@ int lf_dev_fold_step_batch(lf_ctx *const *ctx, int nsteps, const lf_ajtai *aj, c
  * f_0, f_0 coefficients and w_ccs_0, bit-exact with the unsharded step.
  *   lf_dev_fold_step_partial: commit(z) + decompositions + the 1 + 2(K-1)
  *     partial commitments into partial[lf_fold_step_partial_len] (u64; order:
- *     commit(z)'s cm, then y_s[k], s = 0, 1, k = 1 .. K-1)
+ *     commit(z)'s cm, then y_s[k], s = 0, 1, k = 1 .. K-1; on the fused
+ *     X^1024+1 / X^4096+1 decompositions vector 0 is y_1[0] instead -- commit(z)
+ *     is contracted as the new witness's digit plane 0, and finish forms
+ *     cm = sum_k b_small^k y_1[k] from the summed vectors. The length is the same,
+ *     and either way the buffer is only to be summed over ranks and handed to
+ *     lf_dev_fold_step_finish with the same scheme, params and buffers)
  *   lf_dev_fold_step_finish: given their sum over ranks, the rest of the step
  *   lf_dev_fold_step_sharded: partial, RCCL all-reduce mod p over `comm`, finish
  * Without an RCCL communicator (comm == NULL) the sharded step is lf_dev_fold_step. */

@@ -30,8 +30,11 @@ struct PhaseTimer {
 //    the 2(K-1) commitments of commit_witnesses (:178-201), plus -- when
 //    `commit_f` is given (the device step) -- commit(z)'s A.f in the same pass
 //    over A (29 vectors, one read of A). Result v goes to dst[v]: commit(z)'s
-//    cm first, then y_s[k], s = 0, 1, k = 1 .. K-1.
-//  fold_finish: y_0 = cm - sum b^k y_k of both sides, cm_0 = sum rho_i y_i,
+//    cm first, then y_s[k], s = 0, 1, k = 1 .. K-1. On the fused X^1024 + 1 and
+//    X^4096 + 1 decompositions vector 0 is side 1's plane-0 operand row instead
+//    (z_plane0 below) and its result y_1[0]: no pass converts f.
+//  fold_finish: y_0 = cm - sum b^k y_k of both sides (cm1_out: side 1's y_0 is
+//    given and cm = sum b^k y_k is made instead), cm_0 = sum rho_i y_i,
 //    f_0 = sum rho_i f_i (folding.rs:258-268, folding/utils.rs:470-476) and
 //    Witness::from_f(f_0) (arith.rs:299-313).
 // d = 4096 with b_small = 2 has the register-transform decomposition (kernels_n4k.hip)
@@ -66,11 +69,32 @@ StepPlan step_plan(const lf_ajtai *aj, const lf_params *pr, int lbs, const Table
   return p;
 }
 
+// commit(z) from the decomposition's own rows. The decomposition is exact (f_coeff =
+// sum_k 2^(k lbs) D_k, or the step's error flag is raised) and the NTT is linear, so
+// A f = sum_k 2^(k lbs) A NTT(D_(1,k)): cm = sum_k 2^(k lbs) y_1[k]. A step that
+// commits z on the fused X^1024 + 1 / X^4096 + 1 decompositions therefore has side
+// 1's plane 0 written as operand row 0, contracts it as vector 0 into y_1[0], and
+// fold_finish forms cm from the y_1[k] (y0_cm0's cm1_out). A function of (scheme,
+// params, buffers) alone, never context state: fold_commit, fold_dst and fold_finish
+// each evaluate it, so the split calls (partial / finish) and a failed step cannot
+// disagree.
+bool z_plane0(const lf_ajtai *aj, const lf_params *pr, int lbs, const Tables *t, const lf_fold_step_bufs *b) {
+  const Decomp dec = step_plan(aj, pr, lbs, t, b).dec;
+  return dec == Decomp::Fused1024 || dec == Decomp::Fused4k;
+}
+int z_plane0(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, int lbs, const lf_fold_step_bufs *b, bool &z0) {
+  Tables *t;
+  LF_TRY(get_tables(c, pr->d, t));
+  z0 = z_plane0(aj, pr, lbs, t, b);
+  return LF_OK;
+}
+
 // both sides of a step for a fused decomposition: the step buffers and the operand
 // rows, planes 1 .. K-1 of side s from row extra + s (K-1) on and (p0: a step
-// without f_k) plane 0 in row extra + 2 (K-1) + s; returns the mask of those rows
+// without f_k) plane 0 in row extra + 2 (K-1) + s, or (z0: z_plane0) side 1's
+// plane 0 in row 0; returns the mask of those rows
 uint32_t step_sides(lfk::FusedSides &sd, const uint64_t *const *fc, const lf_fold_step_bufs *b, int extra, int K,
-                    bool p0) {
+                    bool p0, bool z0 = false) {
   uint32_t rows = 0;
   sd.nside = 2;
   for (int s = 0; s < 2; s++) {
@@ -79,9 +103,9 @@ uint32_t step_sides(lfk::FusedSides &sd, const uint64_t *const *fc, const lf_fol
     sd.f_k[s] = b->fk[s];
     sd.w_ccs_k[s] = b->wk[s];
     sd.row0[s] = extra + s * (K - 1);
-    sd.row_p0[s] = p0 ? extra + 2 * (K - 1) + s : -1;
+    sd.row_p0[s] = z0 && s == 1 ? 0 : p0 ? extra + 2 * (K - 1) + s : -1;
     for (int k = 1; k < K; k++) rows |= 1u << (sd.row0[s] + k - 1);
-    if (p0) rows |= 1u << sd.row_p0[s];
+    if (sd.row_p0[s] >= 0) rows |= 1u << sd.row_p0[s];
   }
   return rows;
 }
@@ -148,6 +172,8 @@ int fold_commit(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, int lb, int 
   // without f_k buffers the planes exist only as operand rows (step_sides), where
   // fold_finish reads f_0's inputs (k_fold_frag), or stay packed
   const bool no_fk = !b->fk[0] && !b->fk[1];
+  // commit(z) rides as side 1's plane-0 row (row 0, extra = 1) instead of a row made from f
+  const bool z0 = commit_f && z_plane0(aj, pr, lbs, t, b);
   if (b->planes[0] || b->planes[1]) {
     if (!(fused24 || fused || fused4k) || lbs != 1 || !b->planes[0] || !b->planes[1])
       return fail(c, LF_ERR_INVALID_ARG,
@@ -176,7 +202,8 @@ int fold_commit(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, int lb, int 
     st.fold_rows.n = 2 * K;
     for (int s2 = 0; s2 < 2; s2++)
       for (int k = 0; k < K; k++) {
-        st.fold_rows.row[s2 * K + k] = k > 0 ? extra + s2 * (K - 1) + k - 1 : extra + 2 * (K - 1) + s2;
+        const int row_p0 = z0 && s2 == 1 ? 0 : extra + 2 * (K - 1) + s2;  // as step_sides
+        st.fold_rows.row[s2 * K + k] = k > 0 ? extra + s2 * (K - 1) + k - 1 : row_p0;
         st.fold_rows.rho[s2 * K + k] = s2 * K + k;
       }
   } else if (!b->fk[0] || !b->fk[1]) {
@@ -212,8 +239,9 @@ int fold_commit(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, int lb, int 
   // dead units: the planes' operand rows are left unwritten where a unit's plane is zero
   LF_TRY(grow_dead(c, (size_t)aj->geom.nch * 64));
   lfk::FusedSides sd{};
-  // without f_k, plane 0 of each side gets an operand row too (d = 1024 / 4096)
-  const uint32_t rows = step_sides(sd, fc_side, b, extra, K, no_fk && !fused24);
+  // without f_k, plane 0 of each side gets an operand row too (d = 1024 / 4096);
+  // z0: side 1's is row 0, with or without f_k, and row 0's dead units read as zero80
+  const uint32_t rows = step_sides(sd, fc_side, b, extra, K, no_fk && !fused24, z0);
   sd.dead = c->dead;
   st.dead_units = {c->dead, rows};
   if (fused4k) {
@@ -259,7 +287,7 @@ int fold_commit(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, int lb, int 
   st.path = plan.path;
   c->step = st;
   lfk::VecPtrs vp{};
-  if (commit_f) {
+  if (commit_f && !z0) {  // Phi_72: f as operand row 0
     PhaseTimer pt(c, LF_PHASE_TO_FRAG);
     vp.p[0] = commit_f;
     LF_HIP(c, lfk::to_frag(vp, 1, 0, aj->geom, d, true, c->frag, c->cur));
@@ -286,24 +314,27 @@ int fold_commit(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, int lb, int 
   return LF_OK;
 }
 
-// destinations of fold_commit's results in the step buffers
-lfk::OutPtrs fold_dst(const lf_params *pr, const lf_fold_step_bufs *b, size_t kd, uint64_t *commit_cm) {
+// destinations of fold_commit's results in the step buffers; z0 (z_plane0): vector 0
+// of a step that commits z is y_1[0], not cm
+lfk::OutPtrs fold_dst(const lf_params *pr, const lf_fold_step_bufs *b, size_t kd, uint64_t *commit_cm,
+                      bool z0 = false) {
   lfk::OutPtrs dst{};
   const int extra = commit_cm ? 1 : 0;
-  if (commit_cm) dst.p[0] = commit_cm;
+  if (commit_cm) dst.p[0] = z0 ? b->y[1] : commit_cm;
   for (int s = 0; s < 2; s++)
     for (int k = 1; k < pr->K; k++) dst.p[extra + s * (pr->K - 1) + k - 1] = b->y[s] + (size_t)k * kd;
   return dst;
 }
 
 int fold_finish(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, int lb, int lbs, size_t W,
-                const lf_fold_step_bufs *b, const uint64_t *cm_i) {
+                const lf_fold_step_bufs *b, uint64_t *cm_i, bool cm1_out = false) {
   const int d = pr->d, L = pr->L, K = pr->K, nw = 2 * K;
   const size_t N = W * (size_t)L, kappa = aj->kappa;
   Tables *t;
   LF_TRY(get_tables(c, d, t));
-  // y_0 of both sides and cm_0 = sum rho_i y_i in one pass (the y_s[k >= 1] are in place)
-  LF_HIP(c, lfk::y0_cm0(b->acc_cm, cm_i, b->y[0], b->y[1], b->rho, kappa, d, lbs, K, b->cm0, c->cur));
+  // y_0 of both sides and cm_0 = sum rho_i y_i in one pass (the y_s[k >= 1] are in place);
+  // cm1_out: y_1[0] is in place too and cm_i is made from side 1's planes
+  LF_HIP(c, lfk::y0_cm0(b->acc_cm, cm_i, b->y[0], b->y[1], b->rho, kappa, d, lbs, K, b->cm0, c->cur, cm1_out));
   const StepState &st = c->step;
   // the f_k rows of both sides, for the NTT-form fold
   auto fk_rows = [&] {
@@ -558,8 +589,10 @@ int lf_dev_fold_step(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, size_t 
   DevGuard g(c);
   int lb, lbs;
   LF_TRY(step_check(c, aj, pr, W, b, lb, lbs));
-  LF_TRY(step_commit(c, aj, pr, W, b, lb, lbs, fold_dst(pr, b, aj->kappa * (size_t)pr->d, b->cm)));
-  return fold_finish(c, aj, pr, lb, lbs, W, b, b->cm);
+  bool z0;
+  LF_TRY(z_plane0(c, aj, pr, lbs, b, z0));
+  LF_TRY(step_commit(c, aj, pr, W, b, lb, lbs, fold_dst(pr, b, aj->kappa * (size_t)pr->d, b->cm, z0)));
+  return fold_finish(c, aj, pr, lb, lbs, W, b, b->cm, z0);
 }
 
 // nsteps independent steps (one context, stream and buffer set each): every
@@ -583,9 +616,11 @@ int lf_dev_fold_step_batch(lf_ctx *const *cs, int nsteps, const lf_ajtai *aj, co
   for (int s = 0; s < nsteps; s++) LF_TRY(step_check(cs[s], aj, pr, W, bs[s], lb, lbs));
   const size_t kd = aj->kappa * (size_t)pr->d;
   Deferred dfr[LF_MAX_STEPS];
+  bool z0[LF_MAX_STEPS];
   for (int s = 0; s < nsteps; s++) {
     DevGuard gs(cs[s]);
-    LF_TRY(step_commit(cs[s], aj, pr, W, bs[s], lb, lbs, fold_dst(pr, bs[s], kd, bs[s]->cm), &dfr[s]));
+    LF_TRY(z_plane0(cs[s], aj, pr, lbs, bs[s], z0[s]));
+    LF_TRY(step_commit(cs[s], aj, pr, W, bs[s], lb, lbs, fold_dst(pr, bs[s], kd, bs[s]->cm, z0[s]), &dfr[s]));
   }
   // steps whose path has no fragments contracted on their own already
   const uint4 *ff[LF_MAX_STEPS];
@@ -632,7 +667,7 @@ int lf_dev_fold_step_batch(lf_ctx *const *cs, int nsteps, const lf_ajtai *aj, co
   }
   for (int s = 0; s < nsteps; s++) {
     DevGuard gs(cs[s]);
-    LF_TRY(fold_finish(cs[s], aj, pr, lb, lbs, W, bs[s], bs[s]->cm));
+    LF_TRY(fold_finish(cs[s], aj, pr, lb, lbs, W, bs[s], bs[s]->cm, z0[s]));
   }
   return LF_OK;
 }
@@ -660,10 +695,13 @@ int lf_dev_fold_step_finish(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, 
   LF_TRY(step_check(c, aj, pr, W, b, lb, lbs));
   if (!partial_sum) return fail(c, LF_ERR_INVALID_ARG, "null partial sum");
   const size_t kd = aj->kappa * (size_t)pr->d;
-  const lfk::OutPtrs dst = fold_dst(pr, b, kd, b->cm);
+  // the all-reduce is linear: vector 0's sum is cm, or (z_plane0) y_1[0]
+  bool z0;
+  LF_TRY(z_plane0(c, aj, pr, lbs, b, z0));
+  const lfk::OutPtrs dst = fold_dst(pr, b, kd, b->cm, z0);
   for (int v = 0; v < fold_nvec(pr, true); v++)
     LF_HIP(c, hipMemcpyAsync(dst.p[v], partial_sum + v * kd, kd * 8, hipMemcpyDeviceToDevice, c->cur));
-  return fold_finish(c, aj, pr, lb, lbs, W, b, b->cm);
+  return fold_finish(c, aj, pr, lb, lbs, W, b, b->cm, z0);
 }
 
 // the decomposition half of fold() without commit(z): both sides' decompose_witness

@@ -869,7 +869,11 @@ __global__ void k_commit_y0(const uint64_t *cm, uint64_t *y, size_t n, int lbs, 
 // flight together instead of one latency per plane (W = 464: 18.6 us per launch
 // with the loads inside the chain)
 constexpr int Y0_KMAX = 16;
-__global__ void k_y0_cm0(const uint64_t *cm0s, const uint64_t *cm1s, uint64_t *y0, uint64_t *y1,
+// CM1: side 1's y_0 is the input (the step contracted the side's plane-0 operand
+// row, api_step.hip) and its commitment the output, cm1 = y_1[0] + sum_{k>=1}
+// 2^(k lbs) y_1[k]: the same loads and the same Horner chain, one sum the other way
+template <bool CM1>
+__global__ void k_y0_cm0(const uint64_t *cm0s, uint64_t *cm1s, uint64_t *y0, uint64_t *y1,
                          const uint64_t *rho, size_t n, int d, int lbs, int K, uint64_t *cm0) {
   const size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   if (c >= n) return;
@@ -894,8 +898,14 @@ __global__ void k_y0_cm0(const uint64_t *cm0s, const uint64_t *cm1s, uint64_t *y
         gl::cacc_mad(a, rv[k], yv[k]);
         acc = gl::mul_pow2(gl::add(acc, yv[k]), lbs);
       }
-    const uint64_t v0 = gl::sub((side ? cm1s : cm0s)[c], acc);
-    y[c] = v0;
+    uint64_t v0;
+    if (CM1 && side) {
+      v0 = y[c];
+      cm1s[c] = gl::add(v0, acc);
+    } else {
+      v0 = gl::sub((side ? cm1s : cm0s)[c], acc);
+      y[c] = v0;
+    }
     gl::cacc_mad(a, rs[0], v0);
   }
   cm0[c] = gl::cacc_reduce(a);
@@ -1681,17 +1691,23 @@ hipError_t sum_planes_to(const uint64_t *partial, int nsplit, size_t len, int nv
   return hipGetLastError();
 }
 
-hipError_t y0_cm0(const uint64_t *cm0s, const uint64_t *cm1s, uint64_t *y0, uint64_t *y1, const uint64_t *rho,
-                  size_t kappa, int d, int lbs, int K, uint64_t *cm0, hipStream_t st) {
+hipError_t y0_cm0(const uint64_t *cm0s, uint64_t *cm1s, uint64_t *y0, uint64_t *y1, const uint64_t *rho,
+                  size_t kappa, int d, int lbs, int K, uint64_t *cm0, hipStream_t st, bool cm1_out) {
   const size_t n = kappa * (size_t)d;
   if (n == 0) return hipSuccess;
-  if (K < 1 || K > Y0_KMAX) return hipErrorInvalidValue;
+  if (K < 1 || K > Y0_KMAX || (cm1_out && d == 24)) return hipErrorInvalidValue;
+  if (cm1_out) {
+    hipLaunchKernelGGL(k_y0_cm0<true>, dim3(blocks(n, 256)), dim3(256), 0, st, cm0s, cm1s, y0, y1, rho, n, d, lbs, K,
+                       cm0);
+    return hipGetLastError();
+  }
   if (d == 24) {
     hipLaunchKernelGGL(k_y0_cm0_phi72, dim3(blocks(kappa * 8, 16)), dim3(256), 0, st, cm0s, cm1s, y0, y1, rho,
                        kappa * 8, lbs, K, cm0);
     return hipGetLastError();
   }
-  hipLaunchKernelGGL(k_y0_cm0, dim3(blocks(n, 256)), dim3(256), 0, st, cm0s, cm1s, y0, y1, rho, n, d, lbs, K, cm0);
+  hipLaunchKernelGGL(k_y0_cm0<false>, dim3(blocks(n, 256)), dim3(256), 0, st, cm0s, cm1s, y0, y1, rho, n, d, lbs, K,
+                     cm0);
   return hipGetLastError();
 }
 

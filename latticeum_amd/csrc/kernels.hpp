@@ -85,8 +85,11 @@ hipError_t sum_planes_to(const uint64_t *partial, int nsplit, size_t len, int nv
 // the fold step's epilogue over the kappa d commitment slots, both sides:
 // y_s[0] = cm_s - sum_{k>=1} 2^(k lbs) y_s[k] (decomposition.rs:183-200), then
 // cm0 = sum_{s,k} rho_{sK+k} (.) y_s[k] (folding/utils.rs:470-476); X^d + 1 rings
-hipError_t y0_cm0(const uint64_t *cm0s, const uint64_t *cm1s, uint64_t *y0, uint64_t *y1, const uint64_t *rho,
-                  size_t kappa, int d, int lbs, int K, uint64_t *cm0, hipStream_t st);
+// and Phi_72. cm1_out (X^d + 1 only): y_1[0] is given and side 1's commitment is
+// the output, cm1s = sum_{k>=0} 2^(k lbs) y_1[k] (a step that contracted side 1's
+// plane-0 operand row instead of commit(z)'s f, api_step.hip)
+hipError_t y0_cm0(const uint64_t *cm0s, uint64_t *cm1s, uint64_t *y0, uint64_t *y1, const uint64_t *rho,
+                  size_t kappa, int d, int lbs, int K, uint64_t *cm0, hipStream_t st, bool cm1_out = false);
 
 // i8-MFMA Ajtai (ajtai_mfma.hip): negacyclic rings and Phi_72, nvec <= 32,
 // kappa <= 32 LF_MAX_KTILES: A is stored as mfma_ktiles(kappa) tiles of 32 rows,

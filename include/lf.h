@@ -35,6 +35,8 @@
  *   zkvm/src/commitments.rs:192-340 vm_mem_comm, vm_mem_comm_with_opening, vm_code_comm
  *                                                              -> lf_vm_mem_comm, lf_dev_merkle_tree,
  *                                                                 lf_merkle_open, lf_vm_code_comm
+ *   zkvm/src/main.rs:132-137 vm_mem_comm_with_opening on every memory op, over a tree
+ *       that stays on the device                               -> lf_memtree_*
  *   latticefold/src/nifs.rs:28-34 LFProof (ark CanonicalSerialize) -> lf_lfproof_serialize
  *       zkvm/src/main.rs:231-234 (serialized_size); the LCCCS layout (lf_lcccs_(de)serialize)
  *       is this project's own (the reference serialises no LCCCS)
@@ -551,6 +553,52 @@ int lf_vm_code_comm(lf_ctx *ctx, const uint8_t *code, size_t len, uint64_t out4[
 int lf_dev_hash_w8_rows(lf_ctx *ctx, const uint64_t *rows, size_t nrows, size_t width, uint64_t *out);
 void lf_hash_w8(const uint64_t *in, size_t n, uint64_t out4[4]);
 int lf_vm_mem_comm(const uint32_t *words, size_t nwords, uint64_t out4[4]);
+
+/* ------------------------------------------------------------ persistent VM memory tree
+ * vm_mem_comm_with_opening (commitments.rs:222-262) is called on every load and store
+ * (main.rs:132-137) and rebuilds the whole tree; one op changes one leaf and the nodes
+ * above it. An lf_memtree keeps the tree on the device (lf_dev_merkle_tree's layout) and
+ * a host mirror of the words, and lf_memtree_apply takes a chunk of the VM's memory-op
+ * log: record j is the reference's MemoryPageComm (root, page, path, page index) after
+ * ops 0..j, the k ops of a batch going up the tree level by level in parallel.
+ *   create: pages >= 1 pages of words_per_page (a power of two) u32 words, at most 2^30
+ *     words in all; uploads the words once and builds the tree
+ *   address: as physical_addr (vm/src/riscvm/vm.rs:395-420): the low two bits are
+ *     dropped, then log2(words_per_page) word-in-page bits, the rest is the page. An
+ *     address past the memory anywhere in a batch: LF_ERR_INVALID_ARG, nothing applied
+ *   apply: is_write == 0 leaves the memory as it is and still yields its record.
+ *     roots [k][4]; pages_out [k][words_per_page] (the touched page after the op), paths
+ *     [k][depth][4] (what lf_merkle_open gives on a rebuilt tree) and page_index [k] may
+ *     be NULL. k == 0 is LF_OK. Synchronous: the host buffers are filled on return, and
+ *     the handle holds the state after op k - 1. Batches are cut into chunks of
+ *     lf_memtree_chunk() = 4096 ops internally (about 8 MB of scratch at 8192 x 256);
+ *     results do not depend on it. A device error during apply leaves the handle
+ *     unusable (every later apply fails)
+ *   root / depth: the current root (host copy, no device call); the path length
+ *   nodes_device: lf_merkle_nodes_len(pages) x 4 words, = lf_dev_merkle_tree of the
+ *     current memory; nodes_host copies them out (synchronises)
+ *   plan (host only, no context): the dependency tables apply() builds per chunk, from
+ *     the ops' page indices p_j (each < pages), depth = the tree's path length:
+ *       prev[j][l], l < depth: the largest j' < j with (p_j' >> l) == ((p_j >> l) ^ 1), or
+ *         -1: the latest earlier op that rewrote the sibling of op j's node in layer l
+ *       last[j][l], l <= depth: 1 if no j'' > j has (p_j'' >> l) == (p_j >> l)
+ *     reads count as ops in both. O(k depth) time and space
+ * The handle belongs to its context (threading as the context's) and must be destroyed
+ * before it. */
+typedef struct lf_memtree lf_memtree;
+typedef struct {
+  uint32_t address, value, is_write; /* vm MemoryOperation (inst.rs:77-82) without the cycle */
+} lf_mem_op;
+int lf_memtree_create(lf_ctx *ctx, const uint32_t *words, size_t pages, size_t words_per_page, lf_memtree **out);
+void lf_memtree_destroy(lf_memtree *t);
+int lf_memtree_root(const lf_memtree *t, uint64_t out4[4]);
+size_t lf_memtree_depth(const lf_memtree *t);
+size_t lf_memtree_chunk(void);
+int lf_memtree_apply(lf_memtree *t, const lf_mem_op *ops, size_t k, uint64_t *roots, uint32_t *pages_out,
+                     uint64_t *paths, uint32_t *page_index);
+const uint64_t *lf_memtree_nodes_device(const lf_memtree *t);
+int lf_memtree_nodes_host(const lf_memtree *t, uint64_t *out);
+int lf_memtree_plan(size_t pages, const uint32_t *page_of_op, size_t k, int32_t *prev, uint8_t *last);
 
 /* ------------------------------------------------------------ wire format
  * LFProof: ark-serialize 0.5 CanonicalSerialize as derived on the reference's

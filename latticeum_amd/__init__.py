@@ -412,6 +412,11 @@ class Context:
         self.check(self.lib.lf_vm_code_comm(self.h, buf, len(code), _ptr(out)))
         return out
 
+    def memtree(self, words, pages: int, words_per_page: int) -> "MemTree":
+        """a Merkle tree of VM memory that stays on the device between memory ops
+        (lf_memtree_create): words = the [pages][words_per_page] u32 memory"""
+        return MemTree(self, words, pages, words_per_page)
+
     def dev_poseidon2_permute(self, t):
         self.check(self.lib.lf_dev_poseidon2_permute(self.h, _dptr(t), t.numel() // 16))
 
@@ -424,6 +429,62 @@ class Context:
         out = C.c_uint64(0)
         self.check(self.lib.lf_dev_linf_norm(self.h, _dptr(t), t.numel(), C.byref(out)))
         return out.value
+
+
+class MemTree:
+    """lf_memtree: the memory tree on the device plus a host mirror of the words.
+    ``apply`` takes a chunk of the VM's memory-op log and returns, per op, the
+    reference's MemoryPageComm after that op (commitments.rs:222-262)."""
+
+    def __init__(self, ctx: Context, words, pages: int, words_per_page: int):
+        self.ctx = ctx
+        self.h = None
+        w = np.ascontiguousarray(np.asarray(words, dtype=np.uint32)).ravel()
+        if w.size != pages * words_per_page:
+            raise ValueError(f"memtree: {w.size} words for {pages} x {words_per_page}")
+        h = C.c_void_p()
+        ctx.check(ctx.lib.lf_memtree_create(ctx.h, _ptr(w) if w.size else None, pages, words_per_page, C.byref(h)))
+        self.h = h
+        self.pages, self.words_per_page = pages, words_per_page
+        self.depth = ctx.lib.lf_memtree_depth(h)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.lf_memtree_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def root(self) -> np.ndarray:
+        out = np.zeros(4, np.uint64)
+        self.ctx.check(self.ctx.lib.lf_memtree_root(self.h, _ptr(out)))
+        return out
+
+    def apply(self, ops):
+        """ops [k][3] = (address, value, is_write) -> (roots [k][4], pages
+        [k][words_per_page], paths [k][depth][4], page_index [k]), record j after ops 0..j"""
+        o = np.ascontiguousarray(np.asarray(ops, dtype=np.uint32)).reshape(-1, 3)
+        k = o.shape[0]
+        roots = np.zeros((k, 4), np.uint64)
+        pages = np.zeros((k, self.words_per_page), np.uint32)
+        paths = np.zeros((k, self.depth, 4), np.uint64)
+        index = np.zeros(k, np.uint32)
+        self.ctx.check(self.ctx.lib.lf_memtree_apply(self.h, _ptr(o), k, _ptr(roots), _ptr(pages), _ptr(paths),
+                                                     _ptr(index)))
+        return roots, pages, paths, index
+
+    def nodes(self) -> np.ndarray:
+        """the device tree, merkle_nodes_len(pages) x 4 words (a device-to-host copy)"""
+        out = np.zeros(4 * merkle_nodes_len(self.pages), np.uint64)
+        self.ctx.check(self.ctx.lib.lf_memtree_nodes_host(self.h, _ptr(out)))
+        return out
+
+    def nodes_device(self) -> int:
+        return self.ctx.lib.lf_memtree_nodes_device(self.h)
 
 
 class Communicator:
@@ -1059,6 +1120,26 @@ def merkle_depth(nrows: int) -> int:
     return k
 
 
+def memtree_chunk() -> int:
+    """ops MemTree.apply handles per internal chunk (lf_memtree_chunk)"""
+    return load().lf_memtree_chunk()
+
+
+def memtree_plan(pages: int, page_of_op):
+    """the dependency tables of a batch of memory ops (lf_memtree_plan, host only):
+    prev [k][depth] int32 and last [k][depth + 1] uint8 from the ops' page indices"""
+    pg = np.ascontiguousarray(np.asarray(page_of_op, dtype=np.uint32)).ravel()
+    k, depth = pg.size, merkle_depth(pages)
+    prev = np.zeros((k, depth), np.int32)
+    last = np.zeros((k, depth + 1), np.uint8)
+    lib = load()
+    rc = lib.lf_memtree_plan(pages, _ptr(pg) if k else None, k, _ptr(prev) if prev.size else None,
+                             _ptr(last) if k else None)
+    if rc:
+        raise LfError(rc, lib.lf_status_string(rc).decode())
+    return prev, last
+
+
 def hash_w8(vals) -> np.ndarray:
     """PaddingFreeSponge<Poseidon2Goldilocks<8>, 8, 4, 4>::hash_iter (host)"""
     x = np.ascontiguousarray(np.asarray(vals, dtype=np.uint64)) if len(vals) else np.zeros(1, np.uint64)
@@ -1080,6 +1161,7 @@ def vm_mem_comm(words) -> np.ndarray:
 
 __all__ = ["Context", "AjtaiCommitmentScheme", "Communicator", "Comb", "CCSMatrices", "Prover", "witness_split_w", "Poseidon2Transcript",
            "LfParams", "LfFoldStepBufs", "merkle_nodes_len", "merkle_depth", "hash_w8", "vm_mem_comm",
+           "MemTree", "memtree_plan", "memtree_chunk",
            "LfError", "goldilocks_dp", "short_challenge", "hash_iter", "hash_iter_states", "acc_comm",
            "ivc_step_comm", "state_i_comm", "vm_regs_comm", "vm_mem_ops_vec_comm", "fold_verify",
            "VerificationError", "RelationError", "P", "REPR_CANONICAL",

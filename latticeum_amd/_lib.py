@@ -165,6 +165,15 @@ SIGNATURES = {
     "lf_vm_code_comm": (I, [VP, VP, SZ, VP]),
     "lf_hash_w8": (None, [VP, SZ, VP]),
     "lf_vm_mem_comm": (I, [VP, SZ, VP]),
+    "lf_memtree_create": (I, [VP, VP, SZ, SZ, C.POINTER(VP)]),
+    "lf_memtree_destroy": (None, [VP]),
+    "lf_memtree_root": (I, [VP, VP]),
+    "lf_memtree_depth": (SZ, [VP]),
+    "lf_memtree_chunk": (SZ, []),
+    "lf_memtree_apply": (I, [VP, VP, SZ, VP, VP, VP, VP]),
+    "lf_memtree_nodes_device": (VP, [VP]),
+    "lf_memtree_nodes_host": (I, [VP, VP]),
+    "lf_memtree_plan": (I, [SZ, VP, SZ, VP, VP]),
     "lf_lcccs_serialize": (I, [C.POINTER(LfLcccs), I, VP, SZ, C.POINTER(SZ)]),
     "lf_lcccs_deserialize": (I, [VP, SZ, I, I, VP, SZ, C.POINTER(LfLcccs)]),
     "lf_lfproof_serialize": (I, [C.POINTER(LfLfproof), I, VP, SZ, C.POINTER(SZ)]),

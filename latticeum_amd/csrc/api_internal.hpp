@@ -1,5 +1,5 @@
 // api_internal.hpp -- what the files behind the extern "C" boundary share
-// (lf_api.hip, api_step.hip, api_sumcheck.hip, api_ccs.hip, fold_prove.hip): the
+// (lf_api.hip, api_step.hip, api_sumcheck.hip, api_ccs.hip, api_memtree.hip, fold_prove.hip): the
 // context and the other handles, the error / scratch / host-buffer helpers, and
 // the two transcript steps every Fiat-Shamir loop is made of.
 #pragma once

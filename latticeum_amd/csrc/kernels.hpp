@@ -330,6 +330,23 @@ hipError_t p2w8_permute(uint64_t *states, size_t n, hipStream_t st);
 size_t merkle_nodes(size_t nrows);
 hipError_t merkle_tree(const uint64_t *rows, size_t nrows, size_t width, uint64_t *nodes, hipStream_t st);
 hipError_t hash_w8_rows(const uint64_t *rows, size_t nrows, size_t width, uint64_t *out, hipStream_t st);
+// off[l] = the first node of padded layer l (leaves first, the root's last) -> the
+// depth (layers below the root), or -1 when the tree has more than max_layers layers
+int merkle_layer_offsets(size_t nrows, size_t *off, int max_layers);
+// a batch of k memory ops against a tree that stays on the device (lf_memtree_apply):
+// the leaf versions, one launch per layer, then the write-back of every node's last
+// version into `nodes` (merkle_tree()'s layout over npages rows of `width` words)
+constexpr int MEMTREE_MAX_DEPTH = 32;
+struct MemtreeBatch {
+  const uint32_t *pages;  // [k][width]: op j's page after ops 0..j
+  const uint32_t *pg;     // [k]: op j's page index
+  const int32_t *prev;    // [k][depth]: the latest earlier op under the sibling node of layer l, or -1
+  const uint8_t *last;    // [k][depth + 1]: op j holds the final version of its node in layer l
+  uint64_t *ver;          // [depth + 1][k][4]: the node versions; ver[depth] = the roots
+  uint64_t *paths;        // [k][depth][4]: the sibling in every layer, leaves first
+};
+hipError_t memtree_apply(uint64_t *nodes, size_t npages, size_t width, const MemtreeBatch &b, size_t k,
+                         hipStream_t st);
 
 // ---------------------------------------------------------------- sparse Mz products (mz.hip)
 // the t CCS matrices (m x n, ring-element CSR) on the device, with the

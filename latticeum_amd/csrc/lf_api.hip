@@ -1,9 +1,10 @@
 // lf_api.hip -- the extern "C" boundary (include/lf.h): the context, the twiddle
 // tables, the host-buffer wrappers, the thin lf_dev_* wrappers and the RCCL
 // communicators. The commit+fold step is in api_step.hip, the sumcheck provers in
-// api_sumcheck.hip, the CCS matrices in api_ccs.hip; api_internal.hpp holds what
-// they share. No CPU compute fallback exists: every ring/commit/fold operation
-// runs on the GPU, and creating a context fails loudly without one.
+// api_sumcheck.hip, the CCS matrices in api_ccs.hip, the persistent memory tree in
+// api_memtree.hip; api_internal.hpp holds what they share. No CPU compute fallback
+// exists: every ring/commit/fold operation runs on the GPU, and creating a context
+// fails loudly without one.
 #include <dlfcn.h>
 
 #include <cstdio>

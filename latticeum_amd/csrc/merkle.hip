@@ -157,6 +157,65 @@ __global__ void __launch_bounds__(256) k_merkle_level(const uint64_t *children, 
   if (ok && i < 4) parents[e * 4 + i] = x;
 }
 
+// ---------------------------------------------------------------- persistent memory tree
+// A batch of k memory ops against a tree that stays on the device (lf_memtree_*):
+// op j carries the snapshot of its page after ops 0..j, and ver[l][j] is the digest
+// of the node above that page in layer l after ops 0..j. The sibling a layer needs
+// is the version of the latest earlier op under the sibling node (prev), else the
+// base tree's node, which the layer launches only read.
+//
+// ver[0][j] = the sponge of snapshot j (u32 words; k_merkle_leaves' partial last block)
+__global__ void __launch_bounds__(256) k_memtree_leaves(const uint32_t *pages, size_t k, size_t width,
+                                                       uint64_t *ver0) {
+  const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  const int lane = threadIdx.x & 63, i = lane & 7;
+  const size_t e = t >> 3;
+  const bool ok = e < k;
+  const uint32_t *row = pages + (ok ? e : 0) * width;
+  uint64_t x = 0;
+  for (size_t pos = 0; pos < width; pos += 4) {
+    const size_t take = width - pos < 4 ? width - pos : 4;
+    if ((size_t)i < take) x = row[pos + i];
+    x = permute8_lane(x, lane);
+  }
+  if (ok && i < 4) ver0[e * 4 + i] = x;
+}
+
+// ver[l + 1][j] = permute(left || right)[0..4) of ver[l][j] and its sibling, ordered by
+// bit l of the page; path[j][l] = the sibling. layer: the base tree's layer l
+__global__ void __launch_bounds__(256) k_memtree_layer(const uint64_t *layer, const uint32_t *pg, const int32_t *prev,
+                                                      size_t k, int l, int depth, const uint64_t *ver,
+                                                      uint64_t *ver_next, uint64_t *paths) {
+  const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  const int lane = threadIdx.x & 63, i = lane & 7;
+  const size_t e = t >> 3;
+  const bool ok = e < k;
+  const size_t j = ok ? e : 0;
+  const size_t node = (size_t)pg[j] >> l;
+  const int32_t pv = prev[j * depth + l];
+  const uint64_t own = ver[j * 4 + (i & 3)];
+  const uint64_t sib = pv >= 0 ? ver[(size_t)pv * 4 + (i & 3)] : layer[(node ^ 1) * 4 + (i & 3)];
+  if (ok && i < 4) paths[(j * depth + l) * 4 + i] = sib;
+  uint64_t x = ((i < 4) == ((node & 1) == 0)) ? own : sib;
+  x = permute8_lane(x, lane);
+  if (ok && i < 4) ver_next[j * 4 + i] = x;
+}
+
+// the final version of every touched node goes into the base tree: exactly one op
+// per (layer, node) has last set, so no two threads store to one word
+struct LayerOffsets {
+  size_t off[MEMTREE_MAX_DEPTH + 1];
+};
+__global__ void __launch_bounds__(256) k_memtree_writeback(uint64_t *nodes, LayerOffsets lo, const uint32_t *pg,
+                                                          const uint8_t *last, size_t k, int depth,
+                                                          const uint64_t *ver) {
+  const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  const size_t w = t & 3, jl = t >> 2;
+  if (jl >= k * (size_t)(depth + 1)) return;
+  const size_t j = jl / (depth + 1), l = jl % (depth + 1);
+  if (last[jl]) nodes[4 * (lo.off[l] + ((size_t)pg[j] >> l)) + w] = ver[(l * k + j) * 4 + w];
+}
+
 unsigned nb(size_t n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
@@ -197,6 +256,35 @@ hipError_t merkle_tree(const uint64_t *rows, size_t nrows, size_t width, uint64_
     off += n;
     n = nn;
   }
+  return hipGetLastError();
+}
+
+// the first node of every padded layer, leaves first; the root's is the last entry
+// (depth + 1 entries: merkle_nodes()'s recurrence)
+int merkle_layer_offsets(size_t nrows, size_t *off, int max_layers) {
+  size_t n = nrows <= 1 ? 1 : nrows + nrows % 2, at = 0;
+  int l = 0;
+  for (;; l++) {
+    if (l >= max_layers) return -1;
+    off[l] = at;
+    if (n == 1) return l;
+    at += n;
+    n = n == 2 ? 1 : ((n / 2 + 1) & ~(size_t)1);
+  }
+}
+
+hipError_t memtree_apply(uint64_t *nodes, size_t npages, size_t width, const MemtreeBatch &b, size_t k,
+                         hipStream_t st) {
+  if (!k) return hipSuccess;
+  LayerOffsets lo;
+  const int depth = merkle_layer_offsets(npages, lo.off, MEMTREE_MAX_DEPTH + 1);
+  if (!npages || !width || depth < 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_memtree_leaves, dim3(nb(8 * k)), dim3(256), 0, st, b.pages, k, width, b.ver);
+  for (int l = 0; l < depth; l++)
+    hipLaunchKernelGGL(k_memtree_layer, dim3(nb(8 * k)), dim3(256), 0, st, nodes + 4 * lo.off[l], b.pg, b.prev, k, l,
+                       depth, b.ver + (size_t)l * k * 4, b.ver + (size_t)(l + 1) * k * 4, b.paths);
+  hipLaunchKernelGGL(k_memtree_writeback, dim3(nb(4 * k * (depth + 1))), dim3(256), 0, st, nodes, lo, b.pg, b.last, k,
+                     depth, b.ver);
   return hipGetLastError();
 }
 

@@ -372,6 +372,16 @@ int lf_dev_poseidon2_permute(lf_ctx *ctx, uint64_t *states, size_t n);
  * 4 + 22 + 4 of poseidon2.rs:100-173 in order (debug entry: the reference's only
  * round vector, sages/inverse_mds.sage, pins the initial MDS and round 0) */
 int lf_dev_poseidon2_permute_rounds(lf_ctx *ctx, uint64_t *states, size_t n, int rounds);
+/* test aid: one primitive of the device field arithmetic (gl.hpp, and the slot products of
+ * slot.hpp / ring.hpp on it), elementwise over n device elements: out[i] = op(a[i], b[i]).
+ * op is a code of latticeum_amd/csrc/gl_probe.hpp (enum Op). The accumulator ops read m
+ * operands per element (a, b hold n m of them, 1 <= m <= 4096) and reduce their m products
+ * once; the slot ops take 3-word elements. s is the shift amount of the shifting ops, which
+ * run as one instantiation per constant s except where the op says run-time. b may be NULL
+ * for one-operand ops. Ops whose contract is "weakly reduced" write the raw u64.
+ * LF_ERR_INVALID_ARG (+ lf_ctx_last_error) for an unknown op or an s or m outside its range. */
+int lf_dev_gl_probe(lf_ctx *ctx, int op, const uint64_t *a, const uint64_t *b, int s, int m, uint64_t *out,
+                    size_t n);
 /* synthetic inputs: element i = SplitMix64(seed, i) re-mixed until < p */
 int lf_dev_fill_uniform(lf_ctx *ctx, uint64_t *out, size_t n, uint64_t seed);
 /* out[c] = sum_r in[r][c] mod p  (reduce of all-gathered accumulators) */

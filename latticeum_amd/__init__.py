@@ -420,6 +420,27 @@ class Context:
     def dev_poseidon2_permute(self, t):
         self.check(self.lib.lf_dev_poseidon2_permute(self.h, _dptr(t), t.numel() // 16))
 
+    GL_PROBE_3WORD = (18, 21, 22, 23, 24, 25)  # gl_probe.hpp glp::words: fq3_mul and the slot ops
+
+    def gl_probe(self, op: int, a, b=None, s: int = 0, m: int = 1) -> np.ndarray:
+        """test aid (lf_dev_gl_probe): the device field primitive `op` (csrc/gl_probe.hpp)
+        elementwise over the host u64 arrays a, b; m operands per element for the
+        accumulator ops, 3-word elements for the slot ops"""
+        import torch
+        dev = f"cuda:{self.device}"
+        a = _u64(a)
+        w = 3 if op in self.GL_PROBE_3WORD else 1
+        n = a.size // (max(m, 1) * w)  # the library rejects m < 1
+        if b is not None and _u64(b).size != a.size:
+            raise ValueError("gl_probe: a and b differ in length")
+        ta = torch.from_numpy(a.view(np.int64)).to(dev)
+        tb = torch.from_numpy(_u64(b).view(np.int64)).to(dev) if b is not None else None
+        out = torch.empty(max(n * w, 1), dtype=torch.int64, device=dev)
+        self.check(self.lib.lf_dev_gl_probe(self.h, op, _dptr(ta), _dptr(tb) if tb is not None else None, s, m,
+                                            _dptr(out), n))
+        self.sync()
+        return out.cpu().numpy().view(np.uint64)[:n * w].copy()
+
     def dev_modp_sum(self, inp, nparts: int, length: int, out):
         self.check(self.lib.lf_dev_modp_sum(self.h, _dptr(inp), nparts, length, _dptr(out)))
 

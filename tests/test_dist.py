@@ -64,8 +64,10 @@ def finish_step(part_sum, acc_cm, rho, sides, n):
 
 
 def _worker(rank, world, port, q):
+    # gloo also where a GPU is present (latticeum_amd.dist.init would pick nccl there, and this
+    # exchange is on CPU tensors)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank),
-                      WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+                      WORLD_SIZE=str(world), LOCAL_RANK=str(rank), LATTICEUM_AMD_REHEARSE_ONE_GPU="1")
     import torch.distributed as dist
 
     from latticeum_amd import dist as LD

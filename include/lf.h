@@ -35,6 +35,8 @@
  *   zkvm/src/commitments.rs:192-340 vm_mem_comm, vm_mem_comm_with_opening, vm_code_comm
  *                                                              -> lf_vm_mem_comm, lf_dev_merkle_tree,
  *                                                                 lf_merkle_open, lf_vm_code_comm
+ *   zkvm/src/commitments.rs:264-288 verify_memory_opening      -> lf_merkle_verify, lf_dev_merkle_verify,
+ *                                                                 lf_memtree_verify
  *   zkvm/src/main.rs:132-137 vm_mem_comm_with_opening on every memory op, over a tree
  *       that stays on the device                               -> lf_memtree_*
  *   latticefold/src/nifs.rs:28-34 LFProof (ark CanonicalSerialize) -> lf_lfproof_serialize
@@ -554,7 +556,9 @@ int lf_dev_linf_norm(lf_ctx *ctx, const uint64_t *x, size_t n, uint64_t *norm);
  *     MerkleTree::new PAGE_COUNT one-row matrices, all of height 1, so its root is ONE
  *     sponge over all pages' words in page order -- a strictly sequential chain of
  *     nwords / 4 permutations that runs on the host (the device would run it on one
- *     8-lane group) */
+ *     8-lane group)
+ *   lf_merkle_verify / lf_dev_merkle_verify: verify_memory_opening (:264-288), one
+ *     opening on the host and k of them in one launch (below) */
 int lf_dev_poseidon2_w8_permute(lf_ctx *ctx, uint64_t *states, size_t n);
 size_t lf_merkle_nodes_len(size_t nrows);
 int lf_dev_merkle_tree(lf_ctx *ctx, const uint64_t *rows, size_t nrows, size_t width, uint64_t *nodes);
@@ -563,6 +567,24 @@ int lf_vm_code_comm(lf_ctx *ctx, const uint8_t *code, size_t len, uint64_t out4[
 int lf_dev_hash_w8_rows(lf_ctx *ctx, const uint64_t *rows, size_t nrows, size_t width, uint64_t *out);
 void lf_hash_w8(const uint64_t *in, size_t n, uint64_t out4[4]);
 int lf_vm_mem_comm(const uint32_t *words, size_t nwords, uint64_t out4[4]);
+/* layers below the root = digests lf_merkle_open writes (0 for nrows == 1) */
+size_t lf_merkle_path_len(size_t nrows);
+/* verify_memory_opening / verify_batch over one matrix: hash `row` (width words, the
+ * PaddingFreeSponge of lf_hash_w8), fold it with path[l] by bit l of index
+ * (even: compress(cur, sib); odd: compress(sib, cur)), compare with root.
+ * LF_OK, LF_ERR_VERIFICATION (root mismatch), LF_ERR_INVALID_ARG (nrows == 0,
+ * width == 0, index >= nrows, NULL). Host only. Words are compared as field elements
+ * (a word >= p stands for its residue); path may be NULL when nrows == 1. */
+int lf_merkle_verify(const uint64_t root[4], const uint64_t *row, size_t width, size_t nrows,
+                     size_t index, const uint64_t *path);
+/* rows [k][width] u64, index [k] u32, paths [k][depth][4], roots: k x 4 words, or 4 words
+ * shared by all records when one_root != 0; ok [k] bytes. All device memory; asynchronous.
+ * ok[j] = 1 if record j opens its root, else 0; a record with index[j] >= nrows gets 0
+ * (the index only orders the two children of every layer: it is never an address).
+ * depth = lf_merkle_path_len(nrows). k == 0 is LF_OK with no launch. */
+int lf_dev_merkle_verify(lf_ctx *ctx, const uint64_t *rows, size_t k, size_t width, size_t nrows,
+                         const uint32_t *index, const uint64_t *paths, const uint64_t *roots,
+                         int one_root, uint8_t *ok);
 
 /* ------------------------------------------------------------ persistent VM memory tree
  * vm_mem_comm_with_opening (commitments.rs:222-262) is called on every load and store
@@ -609,6 +631,48 @@ int lf_memtree_apply(lf_memtree *t, const lf_mem_op *ops, size_t k, uint64_t *ro
 const uint64_t *lf_memtree_nodes_device(const lf_memtree *t);
 int lf_memtree_nodes_host(const lf_memtree *t, uint64_t *out);
 int lf_memtree_plan(size_t pages, const uint32_t *page_of_op, size_t k, int32_t *prev, uint8_t *last);
+
+/* Checking memory-op records (host buffers, the layout lf_memtree_apply fills) without a
+ * handle and without the memory: for records that come from another rank, a checkpoint,
+ * or the prover's own self-check. Both calls are synchronous, cut the records into chunks
+ * of lf_memtree_chunk() internally (pinned staging and device scratch kept in the context;
+ * results do not depend on the chunking) and check the shape as lf_memtree_create does
+ * (LF_ERR_INVALID_ARG). k == 0 is LF_OK. */
+/* every record opens its own root (verify_memory_opening per record, one launch per
+ * chunk): *first_bad = the smallest failing j, or -1.
+ * LF_OK / LF_ERR_VERIFICATION. page_index[j] >= pages fails that record. */
+int lf_memtree_verify(lf_ctx *ctx, size_t pages, size_t words_per_page, size_t k, const uint64_t *roots,
+                      const uint32_t *pages_in, const uint64_t *paths, const uint32_t *page_index,
+                      int64_t *first_bad);
+
+enum lf_memlog_check {
+  LF_MEMLOG_OK = 0,
+  LF_MEMLOG_INDEX = 1,      /* address past the memory, or page_index[j] != page(address_j) */
+  LF_MEMLOG_VALUE = 2,      /* a write whose page does not hold `value` at word(address_j) */
+  LF_MEMLOG_OPENING = 3,    /* (pages_in[j], paths[j], page_index[j]) does not open roots[j] */
+  LF_MEMLOG_TRANSITION = 4  /* read: roots[j] != roots[j-1]; write: pages_in[j] with the word set back
+                             * to old_words[j], under the same path, does not open roots[j-1] */
+};
+/* roots[-1] = start_root. Is the log a history of single-word updates from start_root?
+ * Addresses are taken as lf_memtree_apply takes them. old_words[j] is the word before a
+ * write (ignored for reads; may be NULL if the log has no write, LF_ERR_INVALID_ARG
+ * otherwise). *first_bad = the smallest failing op, *failed = its first failed check in
+ * the enum's order; -1 / LF_MEMLOG_OK when all hold. LF_OK / LF_ERR_VERIFICATION.
+ * Two openings per op run in one launch per chunk (the page after the op against roots[j];
+ * for a write, the page before it against roots[j-1]); INDEX, VALUE and a read's
+ * TRANSITION are host comparisons.
+ * What it proves: a path fixes every sibling subtree, so, given collision resistance of
+ * the sponge and the compression, two pages that open roots[j-1] and roots[j] at one
+ * index under one path belong to memories that differ in that page only; the pages differ
+ * in the one word (old_words[j] -> value). Hence every roots[j] is the root of the memory
+ * obtained from a memory with root roots[j-1] by op j.
+ * What it does not check: that a read returns `value` -- the reference's sb and sh ops
+ * carry sub-word values, and lf_memtree_apply ignores a read's value too -- and that
+ * start_root is the root of any particular memory. */
+int lf_memtree_audit(lf_ctx *ctx, size_t pages, size_t words_per_page, const uint64_t start_root[4],
+                     const lf_mem_op *ops, const uint32_t *old_words, size_t k, const uint64_t *roots,
+                     const uint32_t *pages_in, const uint64_t *paths, const uint32_t *page_index,
+                     int64_t *first_bad, int *failed);
 
 /* ------------------------------------------------------------ wire format
  * LFProof: ark-serialize 0.5 CanonicalSerialize as derived on the reference's

@@ -405,6 +405,57 @@ class Context:
         """independent width-8 sponge hashes of nrows rows -> out [nrows][4]"""
         self.check(self.lib.lf_dev_hash_w8_rows(self.h, _dptr(rows), nrows, width, _dptr(out)))
 
+    def dev_merkle_verify(self, rows, k: int, width: int, nrows: int, index, paths, roots, one_root: bool, ok):
+        """verify_memory_opening of k records in one launch (lf_dev_merkle_verify), all device
+        tensors: rows [k][width] u64, index [k] u32, paths [k][depth][4], roots [k][4] (or [4]
+        with one_root) -> ok [k] bytes, 1 = the record opens its root. Asynchronous."""
+        self.check(self.lib.lf_dev_merkle_verify(self.h, _dptr(rows), k, width, nrows, _dptr(index),
+                                                 _dptr(paths) if paths is not None else None, _dptr(roots),
+                                                 int(bool(one_root)), _dptr(ok)))
+
+    @staticmethod
+    def _records(wpp: int, roots, pages_in, paths, index):
+        r = _u64(roots).reshape(-1, 4)
+        k = r.shape[0]
+        pg = np.ascontiguousarray(np.asarray(pages_in, dtype=np.uint32)).reshape(-1)
+        pa = _u64(paths).reshape(-1)
+        ix = np.ascontiguousarray(np.asarray(index, dtype=np.uint32)).reshape(-1)
+        if pg.size != k * wpp or ix.size != k or (k and pa.size % (4 * k)):
+            raise ValueError(f"memory records: {k} roots, {pg.size} page words, {pa.size} path words, {ix.size} indices")
+        opt = lambda a: _ptr(a) if a.size else None
+        return k, (r, pg, pa, ix), (opt(r), opt(pg), opt(pa), opt(ix))
+
+    def memtree_verify(self, pages: int, words_per_page: int, roots, pages_in, paths, index) -> int:
+        """does every record (root, page, path, page index) of MemTree.apply's layout open its
+        own root (lf_memtree_verify)? -> the smallest failing record, or -1"""
+        k, keep, (r, pg, pa, ix) = self._records(words_per_page, roots, pages_in, paths, index)
+        bad = C.c_int64(-1)
+        rc = self.lib.lf_memtree_verify(self.h, pages, words_per_page, k, r, pg, pa, ix, C.byref(bad))
+        if rc != ERR_VERIFICATION:
+            self.check(rc)
+        return bad.value
+
+    def memtree_audit(self, pages: int, words_per_page: int, start_root, ops, old_words, roots, pages_in, paths,
+                      index) -> tuple[int, int]:
+        """is the log ops [k][3] = (address, value, is_write) with its records a history of
+        single-word updates from start_root (lf_memtree_audit)? old_words [k]: the word before
+        every write (None for a log of reads). -> (first failing op or -1, its MEMLOG_* check or 0)"""
+        k, keep, (r, pg, pa, ix) = self._records(words_per_page, roots, pages_in, paths, index)
+        o = np.ascontiguousarray(np.asarray(ops, dtype=np.uint32)).reshape(-1, 3)
+        if o.shape[0] != k:
+            raise ValueError(f"memtree_audit: {o.shape[0]} ops for {k} records")
+        old = None if old_words is None else np.ascontiguousarray(np.asarray(old_words, dtype=np.uint32)).reshape(-1)
+        if old is not None and old.size != k:
+            raise ValueError(f"memtree_audit: {old.size} old words for {k} ops")
+        sr = _u64(start_root)
+        bad, failed = C.c_int64(-1), C.c_int(0)
+        rc = self.lib.lf_memtree_audit(self.h, pages, words_per_page, _ptr(sr), _ptr(o) if k else None,
+                                       _ptr(old) if old is not None and k else None, k, r, pg, pa, ix,
+                                       C.byref(bad), C.byref(failed))
+        if rc != ERR_VERIFICATION:
+            self.check(rc)
+        return bad.value, failed.value
+
     def vm_code_comm(self, code: bytes) -> np.ndarray:
         """zkvm vm_code_comm (commitments.rs:314-340): Merkle root over the code's half-words"""
         out = np.zeros(4, np.uint64)
@@ -904,6 +955,8 @@ class VerificationError(LfError):
 
 
 ERR_NOT_SATISFIED = 14  # lf.h LF_ERR_NOT_SATISFIED
+ERR_VERIFICATION = 12  # lf.h LF_ERR_VERIFICATION
+MEMLOG_OK, MEMLOG_INDEX, MEMLOG_VALUE, MEMLOG_OPENING, MEMLOG_TRANSITION = range(5)  # lf.h lf_memlog_check
 REL_WITNESS_F, REL_WITNESS_W, REL_NORM, REL_CM, REL_V, REL_U, REL_CCS = range(1, 8)  # lf.h lf_relation_check
 RELATION_CHECKS = {REL_WITNESS_F: "f != CRT(f_coeff)", REL_WITNESS_W: "w_ccs != from_f(f).w_ccs",
                    REL_NORM: "linf(f_coeff) >= bound", REL_CM: "cm != A f", REL_V: "v != f_hat(r)",
@@ -1141,6 +1194,26 @@ def merkle_depth(nrows: int) -> int:
     return k
 
 
+def merkle_path_len(nrows: int) -> int:
+    """layers below the root (lf_merkle_path_len; merkle_depth computed by the library)"""
+    return load().lf_merkle_path_len(nrows)
+
+
+def merkle_verify(root, row, nrows: int, index: int, path) -> bool:
+    """ZkVmCommitter::verify_memory_opening (commitments.rs:264-288) on the host
+    (lf_merkle_verify): does row (its width = len(row)) at `index` of a tree over nrows rows
+    open `root` under `path` [depth][4]? False = LF_ERR_VERIFICATION; bad arguments raise"""
+    lib = load()
+    rt, rw, pa = _u64(root), _u64(row).reshape(-1), _u64(path).reshape(-1)
+    if rt.size != 4 or pa.size != 4 * lib.lf_merkle_path_len(nrows):
+        raise ValueError(f"merkle_verify: {rt.size} root words, {pa.size} path words for {nrows} rows")
+    rc = lib.lf_merkle_verify(_ptr(rt), _ptr(rw) if rw.size else None, rw.size, nrows, index,
+                              _ptr(pa) if pa.size else None)
+    if rc not in (0, ERR_VERIFICATION):
+        raise LfError(rc, "lf_merkle_verify: " + lib.lf_status_string(rc).decode())
+    return rc == 0
+
+
 def memtree_chunk() -> int:
     """ops MemTree.apply handles per internal chunk (lf_memtree_chunk)"""
     return load().lf_memtree_chunk()
@@ -1182,7 +1255,8 @@ def vm_mem_comm(words) -> np.ndarray:
 
 __all__ = ["Context", "AjtaiCommitmentScheme", "Communicator", "Comb", "CCSMatrices", "Prover", "witness_split_w", "Poseidon2Transcript",
            "LfParams", "LfFoldStepBufs", "merkle_nodes_len", "merkle_depth", "hash_w8", "vm_mem_comm",
-           "MemTree", "memtree_plan", "memtree_chunk",
+           "MemTree", "memtree_plan", "memtree_chunk", "merkle_path_len", "merkle_verify",
+           "MEMLOG_OK", "MEMLOG_INDEX", "MEMLOG_VALUE", "MEMLOG_OPENING", "MEMLOG_TRANSITION", "ERR_VERIFICATION",
            "LfError", "goldilocks_dp", "short_challenge", "hash_iter", "hash_iter_states", "acc_comm",
            "ivc_step_comm", "state_i_comm", "vm_regs_comm", "vm_mem_ops_vec_comm", "fold_verify",
            "VerificationError", "RelationError", "P", "REPR_CANONICAL",

@@ -175,6 +175,11 @@ SIGNATURES = {
     "lf_memtree_nodes_device": (VP, [VP]),
     "lf_memtree_nodes_host": (I, [VP, VP]),
     "lf_memtree_plan": (I, [SZ, VP, SZ, VP, VP]),
+    "lf_merkle_path_len": (SZ, [SZ]),
+    "lf_merkle_verify": (I, [VP, VP, SZ, SZ, SZ, VP]),
+    "lf_dev_merkle_verify": (I, [VP, VP, SZ, SZ, SZ, VP, VP, VP, I, VP]),
+    "lf_memtree_verify": (I, [VP, SZ, SZ, SZ, VP, VP, VP, VP, C.POINTER(C.c_int64)]),
+    "lf_memtree_audit": (I, [VP, SZ, SZ, VP, VP, VP, SZ, VP, VP, VP, VP, C.POINTER(C.c_int64), C.POINTER(I)]),
     "lf_lcccs_serialize": (I, [C.POINTER(LfLcccs), I, VP, SZ, C.POINTER(SZ)]),
     "lf_lcccs_deserialize": (I, [VP, SZ, I, I, VP, SZ, C.POINTER(LfLcccs)]),
     "lf_lfproof_serialize": (I, [C.POINTER(LfLfproof), I, VP, SZ, C.POINTER(SZ)]),

@@ -90,6 +90,9 @@ struct lf_ctx {
   size_t rel_elems = 0;
   uint64_t *hmsg = nullptr;     // pinned host staging of the sumcheck round messages
   size_t hmsg_elems = 0;
+  uint8_t *mv_host = nullptr;   // lf_memtree_verify / lf_memtree_audit: one chunk's pinned staging
+  uint8_t *mv_dev = nullptr;    // and its device copy, status bytes included
+  size_t mv_bytes = 0;
   bool timing = false;
   hipEvent_t join = nullptr;    // lf_dev_fold_step_batch: this stream's point to wait for / be waited on
   hipStream_t contract = nullptr;  // lf_ctx_set_contract_stream: where batched contractions led by this context run

@@ -81,15 +81,23 @@ static int memtree_reserve(lf_memtree *t, size_t k) {
   return LF_OK;
 }
 
+// the shape of a memory: at least one page of a power-of-two number of words, every
+// word with a 32-bit byte address -> log2(words_per_page)
+static int memtree_shape(lf_ctx *c, size_t pages, size_t words_per_page, int &wbits) {
+  wbits = words_per_page == 1 ? 0 : log2_exact(words_per_page);
+  if (!pages || wbits < 0)
+    return fail(c, LF_ERR_INVALID_ARG, "memtree: at least one page of a power-of-two number of words");
+  if (wbits > 30 || pages > ((size_t)1 << (30 - wbits)))
+    return fail(c, LF_ERR_INVALID_ARG, "memtree: the memory exceeds the 32-bit address space");
+  return LF_OK;
+}
+
 int lf_memtree_create(lf_ctx *c, const uint32_t *words, size_t pages, size_t words_per_page, lf_memtree **out) {
   if (!c || !out) return LF_ERR_INVALID_ARG;
   *out = nullptr;
-  const int wbits = words_per_page == 1 ? 0 : log2_exact(words_per_page);
-  if (!words || !pages || wbits < 0)
-    return fail(c, LF_ERR_INVALID_ARG, "memtree: at least one page of a power-of-two number of words");
-  // every word has a 32-bit byte address
-  if (wbits > 30 || pages > ((size_t)1 << (30 - wbits)))
-    return fail(c, LF_ERR_INVALID_ARG, "memtree: the memory exceeds the 32-bit address space");
+  if (!words) return fail(c, LF_ERR_INVALID_ARG, "memtree: at least one page of a power-of-two number of words");
+  int wbits;
+  LF_TRY(memtree_shape(c, pages, words_per_page, wbits));
   DevGuard g(c);
   auto t = std::make_unique<lf_memtree>();
   t->ctx = c;
@@ -209,5 +217,148 @@ int lf_memtree_plan(size_t pages, const uint32_t *page_of_op, size_t k, int32_t 
     if (page_of_op[j] >= pages) return LF_ERR_INVALID_ARG;
   std::vector<std::unordered_map<uint64_t, int32_t>> maps(depth + 1);
   plan_tables(depth, page_of_op, k, [&maps](int l, uint64_t node) -> int32_t & { return maps[l][node]; }, prev, last);
+  return LF_OK;
+}
+
+// ---------------------------------------------------------------- checking records
+namespace {
+
+// one chunk of k records and ntask (k or 2k) checks, in the context's pinned buffer and
+// its device copy: [roots ntask x 4 | paths k x depth x 4 | rows ntask x wpp u32 |
+// index k u32 | status ntask bytes]
+struct CheckLayout {
+  size_t paths, rows, index, ok, bytes;
+  CheckLayout(size_t k, size_t ntask, size_t wpp, size_t depth) {
+    paths = ntask * 32;
+    rows = paths + k * depth * 32;
+    index = rows + ntask * wpp * 4;
+    ok = (index + k * 4 + 7) & ~(size_t)7;
+    bytes = ok + ntask;
+  }
+};
+
+int check_reserve(lf_ctx *c, size_t bytes) {
+  if (bytes <= c->mv_bytes) return LF_OK;
+  if (c->mv_host) (void)hipHostFree(c->mv_host);
+  if (c->mv_dev) (void)hipFree(c->mv_dev);
+  c->mv_host = c->mv_dev = nullptr;
+  c->mv_bytes = 0;
+  LF_HIP(c, hipHostMalloc((void **)&c->mv_host, bytes, hipHostMallocDefault));
+  LF_HIP(c, hipMalloc((void **)&c->mv_dev, bytes));
+  c->mv_bytes = bytes;
+  return LF_OK;
+}
+
+// the staged chunk up, its ntask checks, the status bytes back into the pinned buffer
+int check_run(lf_ctx *c, const CheckLayout &L, size_t k, size_t ntask, size_t pages, size_t wpp) {
+  uint8_t *d = c->mv_dev;
+  LF_HIP(c, hipMemcpyAsync(d, c->mv_host, L.ok, hipMemcpyHostToDevice, c->cur));
+  LF_HIP(c, lfk::merkle_verify(reinterpret_cast<const uint32_t *>(d + L.rows), ntask, k, wpp, pages,
+                               reinterpret_cast<const uint32_t *>(d + L.index),
+                               reinterpret_cast<const uint64_t *>(d + L.paths), reinterpret_cast<const uint64_t *>(d),
+                               false, d + L.ok, c->cur));
+  LF_HIP(c, hipMemcpyAsync(c->mv_host + L.ok, d + L.ok, ntask, hipMemcpyDeviceToHost, c->cur));
+  LF_HIP(c, hipStreamSynchronize(c->cur));
+  return LF_OK;
+}
+
+bool same_digest(const uint64_t *a, const uint64_t *b) {
+  for (int w = 0; w < 4; w++)
+    if (gl::canon(a[w]) != gl::canon(b[w])) return false;
+  return true;
+}
+
+}  // namespace
+
+int lf_memtree_verify(lf_ctx *c, size_t pages, size_t words_per_page, size_t k, const uint64_t *roots,
+                      const uint32_t *pages_in, const uint64_t *paths, const uint32_t *page_index,
+                      int64_t *first_bad) {
+  if (!c || !first_bad) return LF_ERR_INVALID_ARG;
+  *first_bad = -1;
+  int wbits;
+  LF_TRY(memtree_shape(c, pages, words_per_page, wbits));
+  if (!k) return LF_OK;
+  const size_t wpp = words_per_page, depth = (size_t)lfk::merkle_depth(pages);
+  if (!roots || !pages_in || !page_index || (depth && !paths))
+    return fail(c, LF_ERR_INVALID_ARG, "memtree verify: roots, pages, paths and page indices are required");
+  DevGuard g(c);
+  for (size_t at = 0; at < k; at += MEMTREE_CHUNK) {
+    const size_t kc = std::min(MEMTREE_CHUNK, k - at);
+    const CheckLayout L(kc, kc, wpp, depth);
+    LF_TRY(check_reserve(c, L.bytes));
+    uint8_t *h = c->mv_host;
+    memcpy(h, roots + at * 4, kc * 32);
+    if (depth) memcpy(h + L.paths, paths + at * depth * 4, kc * depth * 32);
+    memcpy(h + L.rows, pages_in + at * wpp, kc * wpp * 4);
+    memcpy(h + L.index, page_index + at, kc * 4);
+    LF_TRY(check_run(c, L, kc, kc, pages, wpp));
+    for (size_t j = 0; j < kc; j++)
+      if (!h[L.ok + j]) {
+        *first_bad = (int64_t)(at + j);
+        return fail(c, LF_ERR_VERIFICATION,
+                    "memtree verify: record " + std::to_string(at + j) + " does not open its root");
+      }
+  }
+  return LF_OK;
+}
+
+int lf_memtree_audit(lf_ctx *c, size_t pages, size_t words_per_page, const uint64_t start_root[4],
+                     const lf_mem_op *ops, const uint32_t *old_words, size_t k, const uint64_t *roots,
+                     const uint32_t *pages_in, const uint64_t *paths, const uint32_t *page_index, int64_t *first_bad,
+                     int *failed) {
+  if (!c || !first_bad || !failed) return LF_ERR_INVALID_ARG;
+  *first_bad = -1;
+  *failed = LF_MEMLOG_OK;
+  int wbits;
+  LF_TRY(memtree_shape(c, pages, words_per_page, wbits));
+  if (!k) return LF_OK;
+  const size_t wpp = words_per_page, depth = (size_t)lfk::merkle_depth(pages);
+  if (!start_root || !ops || !roots || !pages_in || !page_index || (depth && !paths))
+    return fail(c, LF_ERR_INVALID_ARG,
+                "memtree audit: the start root, ops, roots, pages, paths and page indices are required");
+  if (!old_words)
+    for (size_t j = 0; j < k; j++)
+      if (ops[j].is_write) return fail(c, LF_ERR_INVALID_ARG, "memtree audit: a log with writes needs old_words");
+  DevGuard g(c);
+  for (size_t at = 0; at < k; at += MEMTREE_CHUNK) {
+    const size_t kc = std::min(MEMTREE_CHUNK, k - at);
+    // task j: the page after op at + j against its root; task kc + j: the page before it
+    // (the written word set back) against the root before it, under the same path
+    const CheckLayout L(kc, 2 * kc, wpp, depth);
+    LF_TRY(check_reserve(c, L.bytes));
+    uint8_t *h = c->mv_host;
+    const uint64_t *before = at ? roots + (at - 1) * 4 : start_root;
+    memcpy(h, roots + at * 4, kc * 32);
+    memcpy(h + kc * 32, before, 32);
+    memcpy(h + kc * 32 + 32, roots + at * 4, (kc - 1) * 32);
+    if (depth) memcpy(h + L.paths, paths + at * depth * 4, kc * depth * 32);
+    uint32_t *post = reinterpret_cast<uint32_t *>(h + L.rows), *pre = post + kc * wpp;
+    memcpy(post, pages_in + at * wpp, kc * wpp * 4);
+    memcpy(pre, post, kc * wpp * 4);
+    for (size_t j = 0; j < kc; j++)
+      if (ops[at + j].is_write) pre[j * wpp + ((ops[at + j].address >> 2) & (wpp - 1))] = old_words[at + j];
+    memcpy(h + L.index, page_index + at, kc * 4);
+    LF_TRY(check_run(c, L, kc, 2 * kc, pages, wpp));
+    const uint8_t *ok_post = h + L.ok, *ok_pre = ok_post + kc;
+    for (size_t j = 0; j < kc; j++) {
+      const lf_mem_op &op = ops[at + j];
+      const size_t word = op.address >> 2, page = word >> wbits;
+      int bad = LF_MEMLOG_OK;
+      if (page >= pages || page_index[at + j] != page)
+        bad = LF_MEMLOG_INDEX;
+      else if (op.is_write && pages_in[(at + j) * wpp + (word & (wpp - 1))] != op.value)
+        bad = LF_MEMLOG_VALUE;
+      else if (!ok_post[j])
+        bad = LF_MEMLOG_OPENING;
+      else if (op.is_write ? !ok_pre[j] : !same_digest(roots + (at + j) * 4, j ? roots + (at + j - 1) * 4 : before))
+        bad = LF_MEMLOG_TRANSITION;
+      if (bad) {
+        *first_bad = (int64_t)(at + j);
+        *failed = bad;
+        return fail(c, LF_ERR_VERIFICATION,
+                    "memtree audit: op " + std::to_string(at + j) + " fails check " + std::to_string(bad));
+      }
+    }
+  }
   return LF_OK;
 }

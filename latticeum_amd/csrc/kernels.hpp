@@ -333,6 +333,16 @@ hipError_t hash_w8_rows(const uint64_t *rows, size_t nrows, size_t width, uint64
 // off[l] = the first node of padded layer l (leaves first, the root's last) -> the
 // depth (layers below the root), or -1 when the tree has more than max_layers layers
 int merkle_layer_offsets(size_t nrows, size_t *off, int max_layers);
+// layers below the root = the length of an opening path
+int merkle_depth(size_t nrows);
+// ok[e] = does (rows[e], index, path) open its root, for e < ntask: rows [ntask][width]
+// (Word = uint64_t or uint32_t), roots [ntask][4] or 4 shared words (one_root), index
+// [span] and paths [span][depth][4], read at e or, for e >= span, at e - span
+// (ntask <= 2 span). An index >= nrows gives 0; it is never an address
+template <class Word>
+hipError_t merkle_verify(const Word *rows, size_t ntask, size_t span, size_t width, size_t nrows,
+                         const uint32_t *index, const uint64_t *paths, const uint64_t *roots, bool one_root,
+                         uint8_t *ok, hipStream_t st);
 // a batch of k memory ops against a tree that stays on the device (lf_memtree_apply):
 // the leaf versions, one launch per layer, then the write-back of every node's last
 // version into `nodes` (merkle_tree()'s layout over npages rows of `width` words)

@@ -375,6 +375,8 @@ void lf_ctx_destroy(lf_ctx *c) {
   if (c->sel) (void)hipFree(c->sel);
   if (c->rel) (void)hipFree(c->rel);
   if (c->hmsg) (void)hipHostFree(c->hmsg);
+  if (c->mv_host) (void)hipHostFree(c->mv_host);
+  if (c->mv_dev) (void)hipFree(c->mv_dev);
   if (c->join) (void)hipEventDestroy(c->join);
   if (c->cjoin) (void)hipEventDestroy(c->cjoin);
   if (c->d_err) (void)hipFree(c->d_err);
@@ -887,6 +889,20 @@ int lf_merkle_open(lf_ctx *c, const uint64_t *nodes, size_t nrows, size_t index,
     k++;
   }
   LF_HIP(c, hipStreamSynchronize(c->cur));
+  return LF_OK;
+}
+
+size_t lf_merkle_path_len(size_t nrows) { return (size_t)lfk::merkle_depth(nrows); }
+
+int lf_dev_merkle_verify(lf_ctx *c, const uint64_t *rows, size_t k, size_t width, size_t nrows, const uint32_t *index,
+                         const uint64_t *paths, const uint64_t *roots, int one_root, uint8_t *ok) {
+  if (!c) return LF_ERR_INVALID_ARG;
+  if (!k) return LF_OK;
+  if (!rows || !index || !roots || !ok || !width || !nrows || (nrows > 1 && !paths) || k > ((size_t)1 << 28))
+    return fail(c, LF_ERR_INVALID_ARG,
+                "Merkle verify: at most 2^28 rows of width >= 1 from a tree of at least one row");
+  DevGuard g(c);
+  LF_HIP(c, lfk::merkle_verify(rows, k, k, width, nrows, index, paths, roots, one_root != 0, ok, c->cur));
   return LF_OK;
 }
 

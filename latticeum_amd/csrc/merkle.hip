@@ -216,9 +216,75 @@ __global__ void __launch_bounds__(256) k_memtree_writeback(uint64_t *nodes, Laye
   if (last[jl]) nodes[4 * (lo.off[l] + ((size_t)pg[j] >> l)) + w] = ver[(l * k + j) * 4 + w];
 }
 
+// ---------------------------------------------------------------- opening checks
+// verify_memory_opening (commitments.rs:264-288) of ntask records, one 8-lane group
+// each: the sponge of the record's row (k_merkle_leaves' for u64 words, k_memtree_leaves'
+// for u32 words), folded with its `depth` siblings by the bits of its index, against its
+// root -> ok[e] = 1 / 0. Task e reads row e and root e (root 0 when root_stride == 0);
+// its index and path are record e's, or record e - span's for e >= span (ntask <= 2 span:
+// the audit's second image of every record, under the same path). The index only
+// orders the two children and is compared with nrows: it is never an address. Inputs
+// come from outside, so every word is canonicalised. Groups past ntask run on a clamped
+// record and store nothing; the sponge length and the depth are wave-uniform.
+__device__ __forceinline__ uint64_t row_word(const uint64_t *row, size_t at) { return gl::canon(row[at]); }
+__device__ __forceinline__ uint64_t row_word(const uint32_t *row, size_t at) { return row[at]; }
+
+template <class Word>
+__global__ void __launch_bounds__(256) k_merkle_verify(const Word *rows, size_t ntask, size_t span, size_t width,
+                                                      size_t nrows, int depth, const uint32_t *index,
+                                                      const uint64_t *paths, const uint64_t *roots,
+                                                      size_t root_stride, uint8_t *ok) {
+  const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  const int lane = threadIdx.x & 63, i = lane & 7;
+  const size_t e = t >> 3;
+  const bool live = e < ntask;
+  const size_t j = live ? e : 0, rec = j >= span ? j - span : j;
+  const Word *row = rows + j * width;
+  uint64_t x = 0;
+  for (size_t pos = 0; pos < width; pos += 4) {
+    const size_t take = width - pos < 4 ? width - pos : 4;
+    if ((size_t)i < take) x = row_word(row, pos + i);
+    x = permute8_lane(x, lane);
+  }
+  const uint32_t idx = index[rec];
+  uint32_t node = idx;
+  const uint64_t *path = paths + rec * (size_t)depth * 4;
+  for (int l = 0; l < depth; l++, node >>= 1) {
+    const uint64_t own = shfl64(x, (lane & ~7) | (i & 3));  // the digest sits in the group's lanes 0..3
+    const uint64_t sib = gl::canon(path[l * 4 + (i & 3)]);
+    x = permute8_lane(((i < 4) == ((node & 1) == 0)) ? own : sib, lane);
+  }
+  int same = i >= 4 || x == gl::canon(roots[j * root_stride + (i & 3)]);
+  same &= __shfl_xor(same, 1);
+  same &= __shfl_xor(same, 2);
+  if (live && i == 0) ok[e] = same && idx < nrows;
+}
+
 unsigned nb(size_t n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
+
+int merkle_depth(size_t nrows) {
+  size_t n = nrows <= 1 ? 1 : nrows + nrows % 2;
+  int l = 0;
+  for (; n > 1; l++) n = n == 2 ? 1 : ((n / 2 + 1) & ~(size_t)1);
+  return l;
+}
+
+template <class Word>
+hipError_t merkle_verify(const Word *rows, size_t ntask, size_t span, size_t width, size_t nrows,
+                         const uint32_t *index, const uint64_t *paths, const uint64_t *roots, bool one_root,
+                         uint8_t *ok, hipStream_t st) {
+  if (!ntask) return hipSuccess;
+  if (!nrows || !width || ntask > 2 * span || ntask > ((size_t)1 << 28)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_merkle_verify<Word>, dim3(nb(8 * ntask)), dim3(256), 0, st, rows, ntask, span, width, nrows,
+                     merkle_depth(nrows), index, paths, roots, one_root ? (size_t)0 : (size_t)4, ok);
+  return hipGetLastError();
+}
+template hipError_t merkle_verify<uint64_t>(const uint64_t *, size_t, size_t, size_t, size_t, const uint32_t *,
+                                            const uint64_t *, const uint64_t *, bool, uint8_t *, hipStream_t);
+template hipError_t merkle_verify<uint32_t>(const uint32_t *, size_t, size_t, size_t, size_t, const uint32_t *,
+                                            const uint64_t *, const uint64_t *, bool, uint8_t *, hipStream_t);
 
 hipError_t p2w8_permute(uint64_t *states, size_t n, hipStream_t st) {
   if (!n) return hipSuccess;

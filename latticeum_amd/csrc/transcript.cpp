@@ -565,4 +565,24 @@ int lf_vm_mem_comm(const uint32_t *words, size_t nwords, uint64_t out4[4]) {
   return LF_OK;
 }
 
+int lf_merkle_verify(const uint64_t root[4], const uint64_t *row, size_t width, size_t nrows, size_t index,
+                     const uint64_t *path) {
+  // verify_memory_opening (commitments.rs:264-288): verify_batch over one matrix. The
+  // layers are the padded ones of lf_dev_merkle_tree, so the sibling of a last odd node
+  // is the zero digest the opening carries like any other
+  if (!root || !row || !width || !nrows || index >= nrows || (nrows > 1 && !path)) return LF_ERR_INVALID_ARG;
+  uint64_t s[8] = {0};
+  lf_hash_w8(row, width, s);
+  size_t n = nrows <= 1 ? 1 : nrows + nrows % 2, i = index;
+  for (size_t l = 0; n > 1; l++, i /= 2, n = n == 2 ? 1 : ((n / 2 + 1) & ~(size_t)1)) {
+    const int own = i % 2 ? 4 : 0;
+    if (own) memcpy(s + 4, s, 32);
+    for (int w = 0; w < 4; w++) s[(own ^ 4) + w] = gl::canon(path[4 * l + w]);
+    permute8(s);
+  }
+  for (int w = 0; w < 4; w++)
+    if (s[w] != gl::canon(root[w])) return LF_ERR_VERIFICATION;
+  return LF_OK;
+}
+
 }  // extern "C"

@@ -26,12 +26,26 @@
 //    vector at a time for consecutive slots (the fused decomposition,
 //    kernels_n32.hip) writes whole 64-B segments; the 4 waves of a contraction
 //    block take 4 consecutive slots and share every fetched line.
-// Contraction order: the 32 columns of chunk c are the 16-column units
-// u = 2c and 2c + 1; unit u = (G, l) = (u / Lp, u % Lp) holds limb l of the
-// groups 16G .. 16G + 15 (column g Lp + l). With Lp = L (the gadget length)
-// one unit is one limb of 16 consecutive groups, which is what a block of the
-// fused decomposition holds at once; Lp = 1 is the natural column order. A and
-// F use the same order, so the contraction is unchanged.
+// Contraction order: the 32 columns of chunk c are the 16-column units at
+// positions 2c and 2c + 1; a unit (G, l) holds limb l of the groups 16G .. 16G + 15
+// (column g Lp + l). With Lp = L (the gadget length) one unit is one limb of 16
+// consecutive groups, which is what a block of the fused decomposition holds at
+// once; Lp = 1 is the natural column order. For Lp > 1 the units of the limbs
+// below the top one come first, group-major, and the top-limb units last, from a
+// chunk boundary on (fragpos.hpp): FragGeom::ptop. A and F use the same order, so
+// the contraction itself does not know it.
+//
+// The top-limb chunks as a class of their own (ajtai_mfma_steps, two or more
+// steps). The top limb of a balanced base-2^15 decomposition of a field element
+// has |digit| <= 8, so of a witness's 15 digit planes at most 4 are nonzero there
+// on any data, and the decomposition leaves the other rows' units unwritten and
+// flagged (DeadUnits). A is the same for every step, so one 32-wide tile may hold
+// rows of different steps: a small kernel lists the (step, row) pairs with a live
+// top-limb unit, the chunks [ptop / 2, nch) are contracted over that list's
+// tiles (at most one per step, far fewer when most rows are dead), and the
+// chunks below over every step's own rows as before. Both classes write split
+// partial planes that sum_planes_to adds; a row absent from the list contributes
+// the zeroed plane, which is its exact value (its operand is zero there).
 //
 // Phi_72 (d = 24, the reference ring): a slot is an Fq3 = Fq[u]/(u^3 - 2^40)
 // element, and a slot product is a product of degree-2 polynomials reduced mod
@@ -60,8 +74,9 @@ FragGeom frag_geom(size_t ncols, int Lp) {
   FragGeom g;
   g.Lp = Lp;
   g.Wp = ncols / Lp;
-  const size_t units = (g.Wp + 15) / 16 * Lp;
-  g.nch = (int)((units + 1) / 2);
+  const size_t nG = frag_groups(g.Wp);
+  g.ptop = (int)frag_ptop(nG, Lp);
+  g.nch = (int)(frag_npos(nG, Lp) / 2);
   return g;
 }
 
@@ -208,6 +223,31 @@ __device__ __forceinline__ void mfma_epilogue(const v16i *acc, int lane, int kt,
     }
   }
 }
+// The top class's epilogue: this lane's output column is one (step, row) entry of
+// the tile; out = that row's kappa x d block of its step's partial plane, or null
+// for a column past the tile's entries. add_kr: the class's first split.
+__device__ __forceinline__ void mfma_epilogue_top(const v16i *acc, int lane, int kt, int kappa, int d, int so,
+                                                  bool add_kr, uint64_t *out, const uint64_t *kr) {
+  const int h = lane >> 5;
+  auto fe = [](int64_t x) { return x < 0 ? (uint64_t)x + gl::P : (uint64_t)x; };
+#pragma unroll
+  for (int i = 0; i < 16; i++) {
+    int32_t x[15];
+#pragma unroll
+    for (int t = 0; t < 15; t++) x[t] = acc[t][i];
+    asm volatile("" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7]),
+                 "+v"(x[8]), "+v"(x[9]), "+v"(x[10]), "+v"(x[11]), "+v"(x[12]), "+v"(x[13]), "+v"(x[14]));
+    int64_t S[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int t = 0; t < 15; t++) S[t >> 2] += (int64_t)x[t] << (8 * (t & 3));
+    uint64_t r = gl::add(fe(S[0] - S[2] - S[3]), gl::mul_pow2(fe(S[1] + S[2]), 32));
+    const int row = 32 * kt + (i & 3) + 8 * (i >> 2) + 4 * h;
+    if (out && row < kappa) {
+      if (add_kr) r = gl::add(r, kr[(size_t)row * d + so]);
+      out[(size_t)row * d + so] = r;
+    }
+  }
+}
 
 // CPOL: cache policy of the operand copies (2 = nt: streaming, for operands far
 // larger than the caches -- A and F are each read once per launch)
@@ -275,11 +315,26 @@ __device__ __forceinline__ v4i gload16(const v4i *p) {
 // same time and A is fetched from HBM once for all of them (the siblings hit
 // that XCD's L2, or the MALL); each step contracts its own operand rows into its
 // own outputs. CPA / CPF: cache policies of the A and F copies.
-template <int CPA, int CPF, int DP>
+// The kernel contracts the chunks [clo, chi) (the whole order, or one of the two
+// classes), split cps chunks at a time, into the partial planes pl0 + split.
+// TOP: the top class. The `step' slot of a block's index is a tile t of the
+// (step, row) list tbl (fragpos.hpp top_compact; tiles past the list return at
+// once); piece j = 4 q + w of the tile is row row_j of step step_j's operand
+// rows, its dead bit that step's flag of that row, and output column v goes to
+// step_v's plane, row row_v. Those are wave-uniform per piece, resolved once
+// here into scalar registers; the chunk loop is the same code.
+template <class T>
+__device__ __forceinline__ T *uniform_ptr(T *p) {
+  const uint64_t x = (uint64_t)(uintptr_t)p;
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)x), hi = __builtin_amdgcn_readfirstlane((uint32_t)(x >> 32));
+  return reinterpret_cast<T *>((uintptr_t)(((uint64_t)hi << 32) | lo));
+}
+template <int CPA, int CPF, int DP, bool TOP>
 __global__ void __launch_bounds__(256, 1) k_ajtai_mfma_ra(const uint4 *Af, const uint64_t *kr, StepOps so_, int nsteps,
                                                          int d, int nch,
                                                          int nvec, int kappa, int direct, int cps, int ktiles,
-                                                         int nbase, size_t tile_u4, int qd) {
+                                                         int nbase, size_t tile_u4, int qd, int clo, int chi, int pl0,
+                                                         const uint32_t *tbl) {
   static_assert(DP >= 3 && DP <= 5, "F buffers: DP x 32 KiB of LDS");
   __shared__ uint4 Fl[DP][32 * 64];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -288,13 +343,18 @@ __global__ void __launch_bounds__(256, 1) k_ajtai_mfma_ra(const uint4 *Af, const
   const int stp = rem / (8 * ktiles), rem2 = rem - stp * 8 * ktiles;
   const int kt = rem2 >> 3, bi = grp * 8 + (rem2 & 7);
   if (bi >= nbase) return;  // uniform over the block
-  const uint4 *Ff = so_.Ff[stp];
-  uint64_t *partial = so_.partial[stp];
-  const OutPtrs &dst = so_.dst[stp];
+  int nent = 0;  // TOP: this tile's entries
+  if (TOP) {
+    nent = top_tile_entries(tbl[0], stp, nsteps);
+    if (nent == 0) return;  // uniform over the block
+  }
+  const uint4 *Ff = so_.Ff[TOP ? 0 : stp];
+  uint64_t *partial = so_.partial[TOP ? 0 : stp];
+  const OutPtrs &dst = so_.dst[TOP ? 0 : stp];
   const int gw = bi * 4 + w;
   const int s = gw % d, js = gw / d;
-  if (js >= (nch + cps - 1) / cps) return;  // uniform over the block
-  const int c0 = js * cps, c1 = min(nch, c0 + cps);
+  if (js >= (chi - clo + cps - 1) / cps) return;  // uniform over the block
+  const int c0 = clo + js * cps, c1 = min(chi, c0 + cps);
   v16i acc[15];
 #pragma unroll
   for (int t = 0; t < 15; t++) acc[t] = (v16i){0};
@@ -307,21 +367,64 @@ __global__ void __launch_bounds__(256, 1) k_ajtai_mfma_ra(const uint4 *Af, const
       dstr[k] = gload16<CPA>(pa + ((size_t)c * 8 + k) * 64);
     }
   };
-  const int nf = __builtin_amdgcn_readfirstlane((nvec - w + 3) >> 2 < 8 ? (nvec - w + 3) >> 2 : 8);  // wave-uniform
+  const int nrow = TOP ? nent : nvec;  // rows of the tile
+  const int nf = __builtin_amdgcn_readfirstlane((nrow - w + 3) >> 2 < 8 ? (nrow - w + 3) >> 2 : 8);  // wave-uniform
+  // TOP: piece q's source rows (its step's operand rows at this slot quad, row
+  // row_q) and flags (null: never dead), as scalars. The step index selects
+  // among the kernel arguments with a uniform compare per step (a per-lane index
+  // into StepOps would send the struct to scratch). Entries are clamped
+  // (top_step, top_row), so a wrong table cannot form an address outside the
+  // launch's buffers.
+  const uint4 *ftq[8];
+  const uint8_t *flq[8];
+  if (TOP) {
+    const int wu = __builtin_amdgcn_readfirstlane(w);
+    const size_t quad = (size_t)__builtin_amdgcn_readfirstlane(s >> 2) * nch * FV_CHUNK;
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+      const uint32_t e = __builtin_amdgcn_readfirstlane(tbl[1 + 32 * stp + 4 * q + wu]);
+      const int est = top_step(e, nsteps), er = top_row(e);
+      const uint4 *f = so_.Ff[0];
+      DeadUnits du = so_.dead[0];
+#pragma unroll
+      for (int k = 1; k < LF_MAX_STEPS; k++) {
+        f = est == k ? so_.Ff[k] : f;
+        du.flags = est == k ? so_.dead[k].flags : du.flags;
+        du.rows = est == k ? so_.dead[k].rows : du.rows;
+      }
+      ftq[q] = uniform_ptr(f + quad + (size_t)er * 64);
+      flq[q] = uniform_ptr(du.flags && ((du.rows >> er) & 1u) ? du.flags + er : (const uint8_t *)nullptr);
+    }
+  }
   // Dead units (DeadUnits: pieces the decomposition did not write, zero): lane l
   // keeps the mask of chunk c0 + l + 64 m in dm[m], bit 2 q + h for this wave's
   // vector 4 q + w in unit 2 c + h; lanes 32 h .. 32 h + 31 copy half h of a
   // vector, and for a dead half they copy zero80's 0x80 bytes (the offset form of
   // 0) instead, so every chunk still issues the same copies (vm_wait_chunk's
-  // counts hold) and the matrix-core work is unchanged; HBM reads of dead units
-  // are gone. Read here, before any operand copy is in flight.
+  // counts hold); HBM reads of dead units are gone, and the products on them go
+  // with the top class, whose tiles leave out the rows that are dead on every
+  // top-limb unit. Read here, before any operand copy is in flight.
   constexpr int NDM = (AJ_CPS + 63) / 64;
-  const DeadUnits du = so_.dead[stp];
-  const bool has_dead = du.flags != nullptr && du.rows != 0;  // uniform
+  const DeadUnits du = so_.dead[TOP ? 0 : stp];
+  const bool has_dead = TOP || (du.flags != nullptr && du.rows != 0);  // uniform
   uint32_t dm[NDM];
 #pragma unroll
   for (int m = 0; m < NDM; m++) dm[m] = 0;
-  if (has_dead) {
+  if (TOP) {
+#pragma unroll
+    for (int m = 0; m < NDM; m++) {
+      const int c = c0 + lane + 64 * m;
+      if (c < c1) {
+        uint32_t bits = 0;
+#pragma unroll
+        for (int q = 0; q < 8; q++)
+          if (q < nf && flq[q])  // uniform
+            bits |= ((uint32_t)(flq[q][(size_t)c * 64] & 1u) << (2 * q)) |
+                    ((uint32_t)(flq[q][(size_t)c * 64 + 32] & 1u) << (2 * q + 1));
+        dm[m] = bits;
+      }
+    }
+  } else if (has_dead) {
 #pragma unroll
     for (int m = 0; m < NDM; m++) {
       const int c = c0 + lane + 64 * m;
@@ -363,13 +466,18 @@ __global__ void __launch_bounds__(256, 1) k_ajtai_mfma_ra(const uint4 *Af, const
 #pragma unroll
     for (int q = 0; q < 8; q++) {
       const int j = 4 * q + w;
-      const uint4 *src = ((dmask >> (2 * q + hl)) & 1u) ? z80 : ft + (size_t)c * FV_CHUNK + j * 64 + fl_pi(j, lane);
+      // TOP: the same expression with the piece's own rows for ft + j 64 (the swizzle stays on the tile row j)
+      const uint4 *live = TOP ? ftq[q] + (size_t)c * FV_CHUNK + fl_pi(j, lane)
+                              : ft + (size_t)c * FV_CHUNK + j * 64 + fl_pi(j, lane);
+      const uint4 *src = ((dmask >> (2 * q + hl)) & 1u) ? z80 : live;
       if (q < nf) __builtin_amdgcn_global_load_lds((const void *)src, (lds_void *)&Fl[buf][j * 64], 16, 0, CPF);
     }
   };
   auto stage_f_piece = [&](int c, int buf, int q, uint32_t dmask) {
     const int j = 4 * q + w;
-    const uint4 *src = ((dmask >> (2 * q + hl)) & 1u) ? z80 : ft + (size_t)c * FV_CHUNK + j * 64 + fl_pi(j, lane);
+    const uint4 *live = TOP ? ftq[q] + (size_t)c * FV_CHUNK + fl_pi(j, lane)
+                            : ft + (size_t)c * FV_CHUNK + j * 64 + fl_pi(j, lane);
+    const uint4 *src = ((dmask >> (2 * q + hl)) & 1u) ? z80 : live;
     __builtin_amdgcn_global_load_lds((const void *)src, (lds_void *)&Fl[buf][j * 64], 16, 0, CPF);
   };
   const int rh = 2 * (lane & 31) + (lane >> 5), fj = rh >> 1;
@@ -433,7 +541,19 @@ __global__ void __launch_bounds__(256, 1) k_ajtai_mfma_ra(const uint4 *Af, const
     }
   }
   const int so = qd ? (s % qd) * 4 + s / qd : s;
-  mfma_epilogue(acc, lane, kt, kappa, nvec, d, so, js, direct, dst, partial, kr);
+  if (TOP) {
+    // column v of the tile -> its entry's row of its step's plane pl0 + js
+    const int v = lane & 31;
+    const uint32_t e = tbl[1 + 32 * stp + v];
+    const int est = top_step(e, nsteps), er = top_row(e);
+    uint64_t *pp = so_.partial[0];
+#pragma unroll
+    for (int k = 1; k < LF_MAX_STEPS; k++) pp = est == k ? so_.partial[k] : pp;
+    uint64_t *out = v < nent && er < nvec ? pp + ((size_t)(pl0 + js) * nvec + er) * kappa * d : nullptr;
+    mfma_epilogue_top(acc, lane, kt, kappa, d, so, js == 0, out, kr);
+  } else {
+    mfma_epilogue(acc, lane, kt, kappa, nvec, d, so, js, direct, dst, partial, kr);  // (the full class's planes are the first ones)
+  }
 }
 
 // ---------------------------------------------------------------- f_0 from the operand rows
@@ -483,7 +603,8 @@ __global__ void k_phi72_interp(const uint64_t *virt, int nvec, size_t kappa, Out
 
 // ---------------------------------------------------------------- row sums of A
 // tmp[i][w] = sum_j A[i][j][w] mod p (thread per (row, word), lazy 3-word sums)
-__global__ void k_rowsum(const uint64_t *A, size_t kappa, size_t ncols, int d, uint64_t *tmp) {
+// over the columns j0, j0 + jstep, .. below ncols
+__global__ void k_rowsum(const uint64_t *A, size_t kappa, size_t ncols, int d, uint64_t *tmp, size_t j0, size_t jstep) {
   const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   if (t >= kappa * (size_t)d) return;
   const size_t i = t / d;
@@ -491,8 +612,12 @@ __global__ void k_rowsum(const uint64_t *A, size_t kappa, size_t ncols, int d, u
   const uint64_t *p = A + i * ncols * d + w;
   gl::Acc a;
   gl::acc_zero(a);
-  for (size_t j = 0; j < ncols; j++) gl::acc_add(a, p[j * d]);
+  for (size_t j = j0; j < ncols; j += jstep) gl::acc_add(a, p[j * d]);
   tmp[t] = gl::acc_reduce(a);
+}
+__global__ void k_kr_sub(const uint64_t *a, const uint64_t *b, size_t n, uint64_t *out) {
+  const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  if (t < n) out[t] = gl::sub(a[t], b[t]);
 }
 // kr[i][so] = FOFF * (row sum at output slot so): the ring slot itself, or for
 // Phi_72 the Toom-3 virtual slot (phi72_eval of the row sum, linear)
@@ -504,14 +629,57 @@ __global__ void k_rowsum_kr(const uint64_t *tmp, size_t kappa, int d, int dv, ui
   const uint64_t r = d == 24 ? ring::phi72_eval(tmp + i * 24, vs) : tmp[i * d + vs];
   kr[t] = gl::mul(FOFF, r);
 }
-size_t ajtai_rowsums_elems(size_t kappa, int d) { return kappa * (size_t)mfma_dim(d); }
+// Lp > 1 (a geometry with a top region): three tables, m = kappa mfma_dim(d) apart --
+// kr over every column, kr_full = kr - kr_top, and kr_top over the top-limb columns
+// (j % Lp == Lp - 1): what the first split of each chunk class adds back
+size_t ajtai_rowsums_elems(size_t kappa, int d, int Lp) { return (Lp > 1 ? 3 : 1) * kappa * (size_t)mfma_dim(d); }
 hipError_t ajtai_rowsums(const uint64_t *A, size_t kappa, size_t ncols, int d, uint64_t *kr, uint64_t *tmp,
-                         hipStream_t st) {
+                         hipStream_t st, int Lp) {
   const size_t n = kappa * (size_t)d, m = kappa * (size_t)mfma_dim(d);
-  hipLaunchKernelGGL(k_rowsum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, A, kappa, ncols, d, tmp);
-  hipLaunchKernelGGL(k_rowsum_kr, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, tmp, kappa, d, mfma_dim(d),
-                     kr);
+  const dim3 gn((unsigned)((n + 255) / 256)), gm((unsigned)((m + 255) / 256));
+  hipLaunchKernelGGL(k_rowsum, gn, dim3(256), 0, st, A, kappa, ncols, d, tmp, (size_t)0, (size_t)1);
+  hipLaunchKernelGGL(k_rowsum_kr, gm, dim3(256), 0, st, tmp, kappa, d, mfma_dim(d), kr);
+  if (Lp > 1) {
+    hipLaunchKernelGGL(k_rowsum, gn, dim3(256), 0, st, A, kappa, ncols, d, tmp, (size_t)(Lp - 1), (size_t)Lp);
+    hipLaunchKernelGGL(k_rowsum_kr, gm, dim3(256), 0, st, tmp, kappa, d, mfma_dim(d), kr + 2 * m);
+    hipLaunchKernelGGL(k_kr_sub, gm, dim3(256), 0, st, kr, kr + 2 * m, m, kr + m);
+  }
   return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- the top class's (step, row) list
+// One block of 1024 threads = (group part gp < 128, row quad q < 8): over every
+// step, the AND of the flag words of rows 4 q .. 4 q + 3 at the nG top positions
+// (a flag is 0 or 1, so bit 0 of a byte survives iff the row is dead on every one
+// of them); a row outside the step's DeadUnits::rows, or of a step without flags,
+// is live. Thread 0 then packs the live (step, row) pairs (top_compact).
+struct StepDead {
+  DeadUnits d[LF_MAX_STEPS];
+};
+__global__ void __launch_bounds__(1024) k_top_list(StepDead sd, int nsteps, int nvec, int ptop, int nG, uint32_t *tbl) {
+  __shared__ uint32_t live[LF_MAX_STEPS];
+  const int tid = threadIdx.x, q = tid & 7, gp = tid >> 3;
+  if (tid < LF_MAX_STEPS) live[tid] = 0;
+  __syncthreads();
+#pragma unroll
+  for (int s = 0; s < LF_MAX_STEPS; s++) {
+    if (s >= nsteps) break;  // uniform
+    const DeadUnits du = sd.d[s];
+    uint32_t lv = 0xFu << (4 * q);  // rows 4 q .. 4 q + 3
+    if (du.flags) {
+      uint32_t a = 0x01010101u;
+      for (int G = gp; G < nG; G += 128)
+        a &= *reinterpret_cast<const uint32_t *>(du.flags + ((size_t)ptop + G) * 32 + 4 * q);
+      uint32_t deadb = 0;
+#pragma unroll
+      for (int b = 0; b < 4; b++) deadb |= ((a >> (8 * b)) & 1u) << (4 * q + b);
+      lv &= ~(deadb & du.rows);
+    }
+    // a row is live if any group part saw it live: dead bits must hold on every part
+    if (lv) atomicOr(&live[s], lv);
+  }
+  __syncthreads();
+  if (tid == 0) (void)top_compact(live, nsteps, nvec, tbl);
 }
 
 // ---------------------------------------------------------------- launchers
@@ -533,9 +701,28 @@ int mfma_nsplit(const FragGeom &g, int d) {
   const int cps = mfma_cps(g, d);
   return (g.nch + cps - 1) / cps;
 }
+// The two chunk classes of a geometry with a top region ([0, ptop / 2) and
+// [ptop / 2, nch)): each is split evenly into the fewest runs of at most
+// mfma_cps() chunks.
+struct ClassSplit {
+  int cps, nsplit;
+};
+static ClassSplit class_split(int n, int cps_max) {
+  const int ns = (n + cps_max - 1) / cps_max;
+  return {ns ? (n + ns - 1) / ns : 1, ns};
+}
+// partial planes per step: the splits of the whole order (none for a single
+// split, which writes the results directly), or both classes' splits
+static size_t mfma_planes(const FragGeom &g, int d) {
+  const size_t nsplit = mfma_nsplit(g, d), whole = nsplit > 1 ? nsplit : 0;
+  if (!g.ptop) return whole;
+  const int cm = mfma_cps(g, d);
+  const size_t cls = class_split(g.ptop / 2, cm).nsplit + class_split(g.nch - g.ptop / 2, cm).nsplit;
+  return whole > cls ? whole : cls;
+}
 size_t mfma_scratch_elems(const FragGeom &g, int d, size_t kappa, int nvec) {
-  const size_t dv = mfma_dim(d), nsplit = mfma_nsplit(g, d);
-  return (nsplit > 1 ? nsplit : 0) * nvec * kappa * dv + (d == 24 ? (size_t)nvec * kappa * dv : 0);
+  const size_t dv = mfma_dim(d);
+  return mfma_planes(g, d) * nvec * kappa * dv + (d == 24 ? (size_t)nvec * kappa * dv : 0);
 }
 
 // operand rows row0 .. row0 + nrows - 1 <- rows.p[0 .. nrows - 1]
@@ -581,9 +768,24 @@ hipError_t to_frag(const VecPtrs &rows, int nrows, int row0, const FragGeom &g, 
 hipError_t ajtai_mfma_steps(const uint4 *Af, const uint64_t *kr, size_t kappa, const FragGeom &g, int d, int nvec,
                             int nsteps,
                             const uint4 *const *Ff, uint64_t *const *partial, const OutPtrs *dst, hipStream_t st,
-                            hipEvent_t ev0, hipEvent_t ev1, const DeadUnits *dead, const uint4 *zero80) {
+                            hipEvent_t ev0, hipEvent_t ev1, const DeadUnits *dead, const uint4 *zero80,
+                            uint32_t *toptbl) {
   const int dv = mfma_dim(d);
   const int ktiles = mfma_ktiles(kappa);
+  // The top-limb chunks as a class of their own. The class adds a list kernel, a
+  // memset and a launch per call and a plane to sum per step, about 80 us at
+  // d = 1024, W = 464, where a saved tile of the top chunks is worth 32 us (2.1 ns per
+  // chunk and slot): it is on where the tiles it can save, nsteps - 1, times the
+  // top chunks' (slot, A tile) count is at least 2^17, three times that break-even.
+  // And from four steps on: the top class's launch has only its few tiles to share
+  // A's top region among, so by itself it is bound by HBM, and with two steps the
+  // one tile it can save does not pay for that (d = 4096, W = 1024, kappa = 64, two
+  // steps: 5.68 ms -> 4.57 + 1.25 ms and 0.16 ms of plane sums).
+  // LATTICEUM_AMD_TOPCLASS (read per launch, for A/B runs and the tests): 0 never, 1 always.
+  const char *tc = getenv("LATTICEUM_AMD_TOPCLASS");
+  const size_t top_work = (size_t)(g.nch - g.ptop / 2) * dv * ktiles * (nsteps - 1);
+  const bool topc = g.ptop > 0 && nsteps >= 2 && toptbl && zero80 && !(tc && tc[0] == '0') &&
+                    ((tc && tc[0] == '1') || (nsteps >= 4 && top_work >= ((size_t)1 << 17)));
   // zero80 (32 pieces of 0x80 bytes) is the copy source of the dead units'
   // operand pieces: required only when some step has dead-unit flags
   bool any_dead = false;
@@ -592,6 +794,7 @@ hipError_t ajtai_mfma_steps(const uint4 *Af, const uint64_t *kr, size_t kappa, c
       nsteps > LF_MAX_STEPS)
     return hipErrorInvalidValue;
   const int nsplit = mfma_nsplit(g, d), cps = mfma_cps(g, d);
+  const size_t plane = (size_t)nvec * kappa * dv;  // u64 of one partial plane
   // the contraction's own outputs: the results (X^d + 1), or Phi_72's virtual-slot sums
   StepOps so{};
   so.zero80 = zero80;
@@ -601,14 +804,11 @@ hipError_t ajtai_mfma_steps(const uint4 *Af, const uint64_t *kr, size_t kappa, c
     so.dst[s] = dst[s];
     if (dead && zero80) so.dead[s] = dead[s];  // dead units read the constant pieces
     if (d == 24) {
-      uint64_t *virt = partial[s] + (nsplit > 1 ? (size_t)nsplit * nvec * kappa * dv : 0);
+      uint64_t *virt = partial[s] + mfma_planes(g, d) * plane;
       for (int v = 0; v < nvec; v++) so.dst[s].p[v] = virt + (size_t)v * kappa * dv;
     }
   }
   if (ev0) (void)hipEventRecord(ev0, st);
-  const size_t waves = (size_t)dv * nsplit;
-  const int nbase = (int)((waves + 3) / 4);
-  const dim3 grid((unsigned)((nbase + 7) / 8 * 8 * ktiles * nsteps));
   const size_t tile_u4 = frag_elems(g, d);
   // F is dv nch 8 KiB per step (A is as large for kappa = 32): streamed past the
   // caches when larger than they are; A too for one step, but not when several
@@ -616,26 +816,63 @@ hipError_t ajtai_mfma_steps(const uint4 *Af, const uint64_t *kr, size_t kappa, c
   // against 7.0 for A staged through LDS and no better at 3 or 5 chunks,
   // DESIGN.md section 7)
   const bool big = (size_t)dv * g.nch * 8192 > STREAM_OUT_BYTES;
-  const int qd = g.qperm ? d / 4 : 0, direct = nsplit == 1 ? 1 : 0;
-#define LF_AJ(CA, CF)                                                                                     \
-  hipLaunchKernelGGL((k_ajtai_mfma_ra<CA, CF, 4>), grid, dim3(256), 0, st, Af, kr, so, nsteps, dv, g.nch, nvec, \
-                     (int)kappa, direct, cps, ktiles, nbase, tile_u4, qd)
-  // batched: A cached so the sibling blocks hit it, F streamed (A/B on one box,
-  // W = 2^14, 2 steps: 49.6 steps/s against 49.2 both streamed, 49.4 both
-  // cached, 48.3 A streamed / F cached)
-  if (big && nsteps == 1)
-    LF_AJ(2, 2);
-  else if (big)
-    LF_AJ(0, 2);
-  else
-    LF_AJ(0, 0);
+  const int qd = g.qperm ? d / 4 : 0;
+  // one launch over the chunks [clo, chi) in NS splits of CPS chunks; SLOTS: the steps, or the top class's tile slots
+#define LF_AJ(CA, CF, TOPC, KR, SLOTS, DIRECT, CPS, NS, CLO, CHI, PL0)                                              \
+  do {                                                                                                              \
+    const int nbase_ = (int)(((size_t)dv * (NS) + 3) / 4);                                                          \
+    const dim3 grid_((unsigned)((nbase_ + 7) / 8 * 8 * ktiles * (SLOTS)));                                          \
+    hipLaunchKernelGGL((k_ajtai_mfma_ra<CA, CF, 4, TOPC>), grid_, dim3(256), 0, st, Af, KR, so, SLOTS, dv, g.nch,  \
+                       nvec, (int)kappa, DIRECT, CPS, ktiles, nbase_, tile_u4, qd, CLO, CHI, PL0,                  \
+                       (const uint32_t *)toptbl);                                                                   \
+  } while (0)
+  int nplanes = nsplit > 1 ? nsplit : 0;  // partial planes to sum per step
+  if (topc) {
+    // The list, then both classes: the chunks below the top region for every step's
+    // own rows (kr_full), and the top region for the list's tiles (kr_top), into
+    // planes of their own that are zeroed first -- a row absent from the list is
+    // exactly zero there. Two launches: the full class's instance is then the
+    // single-class kernel unchanged (registers, LDS, waits), and at the sizes
+    // where the contraction matters both grids are whole multiples of the CU count.
+    const int ctop = g.ptop / 2;
+    const ClassSplit cf = class_split(ctop, cps), ct = class_split(g.nch - ctop, cps);
+    const size_t m = (size_t)kappa * dv;
+    StepDead sdd{};
+    for (int s = 0; s < nsteps; s++) sdd.d[s] = so.dead[s];
+    hipLaunchKernelGGL(k_top_list, dim3(1), dim3(1024), 0, st, sdd, nsteps, nvec, g.ptop, (int)frag_groups(g.Wp),
+                       toptbl);
+    for (int s = 0; s < nsteps; s++) {
+      const hipError_t em = hipMemsetAsync(partial[s] + cf.nsplit * plane, 0, ct.nsplit * plane * sizeof(uint64_t), st);
+      if (em != hipSuccess) return em;
+    }
+    // batched: A cached so the sibling blocks hit it, F streamed when large
+    if (big) {
+      LF_AJ(0, 2, false, kr + m, nsteps, 0, cf.cps, cf.nsplit, 0, ctop, 0);
+      LF_AJ(0, 2, true, kr + 2 * m, nsteps, 0, ct.cps, ct.nsplit, ctop, g.nch, cf.nsplit);
+    } else {
+      LF_AJ(0, 0, false, kr + m, nsteps, 0, cf.cps, cf.nsplit, 0, ctop, 0);
+      LF_AJ(0, 0, true, kr + 2 * m, nsteps, 0, ct.cps, ct.nsplit, ctop, g.nch, cf.nsplit);
+    }
+    nplanes = cf.nsplit + ct.nsplit;
+  } else {
+    const int direct = nsplit == 1 ? 1 : 0;
+    // batched: A cached so the sibling blocks hit it, F streamed (A/B on one box,
+    // W = 2^14, 2 steps: 49.6 steps/s against 49.2 both streamed, 49.4 both
+    // cached, 48.3 A streamed / F cached)
+    if (big && nsteps == 1)
+      LF_AJ(2, 2, false, kr, nsteps, direct, cps, nsplit, 0, g.nch, 0);
+    else if (big)
+      LF_AJ(0, 2, false, kr, nsteps, direct, cps, nsplit, 0, g.nch, 0);
+    else
+      LF_AJ(0, 0, false, kr, nsteps, direct, cps, nsplit, 0, g.nch, 0);
+  }
 #undef LF_AJ
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   if (ev1) (void)hipEventRecord(ev1, st);
   for (int s = 0; s < nsteps; s++) {
-    if (nsplit > 1) {
-      e = sum_planes_to(partial[s], nsplit, kappa * (size_t)dv, nvec, so.dst[s], st);
+    if (nplanes) {
+      e = sum_planes_to(partial[s], nplanes, kappa * (size_t)dv, nvec, so.dst[s], st);
       if (e != hipSuccess) return e;
     }
     if (d == 24) {

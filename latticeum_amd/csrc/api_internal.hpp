@@ -72,6 +72,7 @@ struct lf_ctx {
   uint8_t *dead = nullptr;      // dead-unit flags of the operand rows (lfk::DeadUnits) [2 nch][32]
   size_t dead_elems = 0;
   uint4 *zero80 = nullptr;      // 32 operand pieces of 0x80 bytes: the offset form of 0 (dead units)
+  uint32_t *toptbl = nullptr;   // the batched contraction's top-class (step, row) list (lfk::TOP_TBL_WORDS)
   StepState step{};             // the last fold_commit's fold path and what it reads
   int ncu = 0;                  // compute units of `device`
   uint64_t *stage = nullptr;    // sharded step: the partial commitments [nvec][kappa d]

@@ -654,7 +654,7 @@ int lf_dev_fold_step_batch(lf_ctx *const *cs, int nsteps, const lf_ajtai *aj, co
       LF_HIP(c0, hipEventCreate(&eb));
     }
     LF_HIP(c0, lfk::ajtai_mfma_steps(aj->Af, aj->kr, aj->kappa, aj->geom, pr->d, nvec, n, ff, pp, dd, cst, ea, eb, du,
-                                     c0->zero80));
+                                     c0->zero80, c0->toptbl));
     if (c0->timing) c0->pending.push_back({ea, eb, nvec, n});
     if (c0->contract) {
       if (!c0->cjoin) LF_HIP(c0, hipEventCreateWithFlags(&c0->cjoin, hipEventDisableTiming));

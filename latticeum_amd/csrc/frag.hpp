@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "fragpos.hpp"
 #include "gl.hpp"
 #include "kernels.hpp"
 
@@ -130,9 +131,12 @@ __device__ __forceinline__ size_t fv_index(size_t s, int nch, int c, int r, int 
 }
 
 // column of operand column t (< 32) of chunk c in the contraction order (Lp, Wp: FragGeom)
+// (position 2c + t / 16 -> its unit: fragpos.hpp; a padding position is past Wp)
 __device__ __forceinline__ size_t frag_column(int c, int t, int Lp, size_t Wp, bool &ok) {
-  const size_t u = 2 * (size_t)c + (t >> 4);
-  const size_t G = u / Lp, l = u % Lp, g = 16 * G + (t & 15);
+  size_t G;
+  int l;
+  frag_unit(2 * (size_t)c + (t >> 4), Lp, frag_ptop(frag_groups(Wp), Lp), G, l);
+  const size_t g = 16 * G + (t & 15);
   ok = g < Wp;
   return g * Lp + l;
 }

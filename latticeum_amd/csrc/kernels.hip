@@ -357,8 +357,9 @@ __global__ void __launch_bounds__(256) k_decompose_phi72(FusedSides sd, size_t N
       __syncthreads();
       for (int tk = t; tk < DEC_GROUPS / 16 * L * 40; tk += blockDim.x) {
         const int vs = tk % 40, ul = tk / 40, gh = ul / L, l = ul - gh * L;
-        const size_t u = ((size_t)blockIdx.x * (DEC_GROUPS / 16) + gh) * L + l;  // contraction unit
-        if (u >= 2 * (size_t)nch) continue;
+        const size_t Gu = (size_t)blockIdx.x * (DEC_GROUPS / 16) + gh, nG = frag_groups(W);
+        if (Gu >= nG) continue;
+        const size_t u = frag_pos(Gu, l, L, frag_ptop(nG, L));  // the unit's position in the contraction order
         uint64_t x[16];
 #pragma unroll
         for (int jj = 0; jj < 16; jj++) {
@@ -542,10 +543,10 @@ __global__ void __launch_bounds__(256) k_decompose_phi72_w(FusedSides sd, size_t
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the tile is read before the operand rounds reuse it
     }
+    const size_t u = frag_pos(G, l, L, frag_ptop(frag_groups(W), L));  // position of these 16 columns' unit
     if (frag && sd.dead && gi == 0 && k >= 1 && k < K)  // one lane per plane writes its flag
-      sd.dead[(G * L + l) * 32 + row0 + k - 1] = ((bal >> (16 * kq)) & 0xFFFFull) ? 0 : 1;
+      sd.dead[u * 32 + row0 + k - 1] = ((bal >> (16 * kq)) & 0xFFFFull) ? 0 : 1;
     if (frag && (bal || !sd.dead)) {
-      const size_t u = G * L + l;  // contraction unit of these 16 columns
       const int ch = (int)(u >> 1), uh = (int)(u & 1);
       const bool live_t = !sd.dead || ((bal >> (16 * kq_t)) & 0xFFFFull) != 0;  // this lane's task's plane
 #pragma unroll

@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "fragpos.hpp"
 #include "ring.hpp"
 
 #define LF_MAX_VECS 32
@@ -94,12 +95,14 @@ hipError_t y0_cm0(const uint64_t *cm0s, uint64_t *cm1s, uint64_t *y0, uint64_t *
 // i8-MFMA Ajtai (ajtai_mfma.hip): negacyclic rings and Phi_72, nvec <= 32,
 // kappa <= 32 LF_MAX_KTILES: A is stored as mfma_ktiles(kappa) tiles of 32 rows,
 // frag_elems() uint4 each.
-// Column (contraction) order: 16-column units u = (u / Lp, u % Lp) = limb l of
-// groups 16G..16G+15; nch 32-column chunks.
+// Column (contraction) order: 16-column units (G, l) = limb l of groups
+// 16G..16G+15 at the positions fragpos.hpp gives them (Lp > 1: the top limbs
+// last, from position ptop on); nch 32-column chunks.
 struct FragGeom {
   int Lp;
   size_t Wp;
   int nch;
+  int ptop = 0;  // the first top-limb position (even); 0: no top region (Lp == 1)
   // d = 4096: operand slot sigma(s) = (s % 4) d/4 + s / 4 (quarter-major, the
   // order kernels_n4k.hip produces slots in); the contraction maps it back
   int qperm = 0;
@@ -118,9 +121,12 @@ hipError_t to_frag(const VecPtrs &rows, int nrows, int row0, const FragGeom &g, 
 // cm: contiguous [nvec][kappa d] results, or (cm == nullptr) per-vector destinations dst
 // kr: FOFF times the row sums of A per (row, output slot), ajtai_rowsums (the
 // vector operand rows are in the offset form, frag.hpp fenc)
+// A geometry with a top region keeps three such tables in kr, ajtai_rowsums_elems(.., 1)
+// apart: over every column, over the columns below the top limb, over the top-limb
+// columns (the two chunk classes of a batched contraction, ajtai_mfma_steps)
 hipError_t ajtai_rowsums(const uint64_t *A, size_t kappa, size_t ncols, int d, uint64_t *kr, uint64_t *tmp,
-                         hipStream_t st);
-size_t ajtai_rowsums_elems(size_t kappa, int d);  // u64 of kr; tmp needs kappa d
+                         hipStream_t st, int Lp = 1);
+size_t ajtai_rowsums_elems(size_t kappa, int d, int Lp = 1);  // u64 of kr; tmp needs kappa d
 hipError_t ajtai_mfma(const uint4 *Af, const uint64_t *kr, size_t kappa, const FragGeom &g, int d, const VecPtrs &fv,
                       int nvec,
                       bool f_ready, uint4 *Ff, uint64_t *partial, uint64_t *cm, hipStream_t st,
@@ -128,12 +134,16 @@ hipError_t ajtai_mfma(const uint4 *Af, const uint64_t *kr, size_t kappa, const F
                       const DeadUnits *dead = nullptr, const uint4 *zero80 = nullptr);
 // nsteps (<= LF_MAX_STEPS) independent steps in one pass over A: step s's operand
 // rows Ff[s] (f_ready), scratch partial[s] (mfma_scratch_elems), results dst[s];
-// dead[s] (may be null): step s's dead operand pieces, read as zero80's pieces
+// dead[s] (may be null): step s's dead operand pieces, read as zero80's pieces.
+// toptbl (TOP_TBL_WORDS u32 of device scratch, may be null): with it, two or more
+// steps on a geometry with a top region contract the top-limb chunks as a class
+// of their own, over the rows that are live there only, where those chunks are worth the
+// class's fixed launch costs (LATTICEUM_AMD_TOPCLASS=0: never, =1: always)
 hipError_t ajtai_mfma_steps(const uint4 *Af, const uint64_t *kr, size_t kappa, const FragGeom &g, int d, int nvec,
                             int nsteps,
                             const uint4 *const *Ff, uint64_t *const *partial, const OutPtrs *dst, hipStream_t st,
                             hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, const DeadUnits *dead = nullptr,
-                            const uint4 *zero80 = nullptr);
+                            const uint4 *zero80 = nullptr, uint32_t *toptbl = nullptr);
 
 // d = 1024 kernels on the register-resident 32 x 32 NTT (kernels_n32.hip)
 // W below which from_w_ccs / from_f run one half-wave per (element, limb)

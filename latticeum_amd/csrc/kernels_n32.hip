@@ -758,7 +758,7 @@ __global__ void __launch_bounds__(512, 1) k_decompose_fused(size_t N, int L, int
           for (int i = 0; i < 32; i++) acc[i] = gl::add(gl::mul(acc[i], b_pow), v[i]);
         }
         if (frag && (kb > 0 || row_p0 >= 0)) {
-          const size_t u = B * L + l;  // contraction unit of these 16 columns
+          const size_t u = frag_pos(B, l, L, frag_ptop(frag_groups(W), L));  // position of these 16 columns' unit
           const int row = kb > 0 ? row0 + kb - 1 : row_p0;
           // a unit whose plane is zero on all 16 columns is not written: its flag
           // says so, and the readers take the offset form of 0 there (DeadUnits).

@@ -289,7 +289,7 @@ __global__ void __launch_bounds__(512, 1) k_decompose_n4k_fused(size_t N, int L,
       }
       horner_step(acc, v, l == L - 1, lb, b_pow);
       if (row >= 0) {  // planes k >= 1, and plane 0 when it has a row (the f_k-free steps fold from the rows)
-        const size_t u = B * L + l;  // contraction unit of these 16 columns
+        const size_t u = frag_pos(B, l, L, frag_ptop(frag_groups(W), L));  // position of these 16 columns' unit
         // dead units as in decompose_fused: the four quarter blocks of a unit vote
         // on the same bytes, so they write the same flag
         const int vs = nvote++ & 1;
@@ -478,7 +478,7 @@ __global__ void __launch_bounds__(512, 1) k_decompose_n4k_mx(size_t N, int L, in
       }
       horner_step(acc, v, l == L - 1, lb, b_pow);
       if (row >= 0) {
-        const size_t u = B * L + l;  // contraction unit of these 16 columns
+        const size_t u = frag_pos(B, l, L, frag_ptop(frag_groups(W), L));  // position of these 16 columns' unit
         const int vs = nvote++ & 1;
         if (sd.dead && lane == 0) vote[vs][wib] = live ? 1u : 0u;
         __syncthreads();  // votes visible; every wave done reading the previous unit's staging

@@ -169,9 +169,9 @@ int ajtai_prepare(lf_ctx *c, lf_ajtai *aj) {
   }
   // the offset form's correction per (row, output slot)
   uint64_t *tmp = nullptr;
-  LF_HIP(c, hipMalloc((void **)&aj->kr, lfk::ajtai_rowsums_elems(aj->kappa, aj->d) * sizeof(uint64_t)));
+  LF_HIP(c, hipMalloc((void **)&aj->kr, lfk::ajtai_rowsums_elems(aj->kappa, aj->d, aj->geom.Lp) * sizeof(uint64_t)));
   LF_HIP(c, hipMalloc((void **)&tmp, aj->kappa * (size_t)aj->d * sizeof(uint64_t)));
-  const hipError_t e = lfk::ajtai_rowsums(aj->A, aj->kappa, aj->ncols, aj->d, aj->kr, tmp, c->cur);
+  const hipError_t e = lfk::ajtai_rowsums(aj->A, aj->kappa, aj->ncols, aj->d, aj->kr, tmp, c->cur, aj->geom.Lp);
   const hipError_t e2 = hipStreamSynchronize(c->cur);
   (void)hipFree(tmp);
   LF_HIP(c, e);
@@ -338,6 +338,8 @@ int lf_ctx_create(int device, lf_ctx **out) {
   if (hipMalloc(&c->sink, 4096 * sizeof(uint64_t)) != hipSuccess) return LF_ERR_OUT_OF_MEMORY;
   if (hipMalloc(&c->zero80, 32 * sizeof(uint4)) != hipSuccess) return LF_ERR_OUT_OF_MEMORY;
   if (hipMemset(c->zero80, 0x80, 32 * sizeof(uint4)) != hipSuccess) return LF_ERR_DEVICE;
+  if (hipMalloc(&c->toptbl, lfk::TOP_TBL_WORDS * sizeof(uint32_t)) != hipSuccess) return LF_ERR_OUT_OF_MEMORY;
+  if (hipMemset(c->toptbl, 0, lfk::TOP_TBL_WORDS * sizeof(uint32_t)) != hipSuccess) return LF_ERR_DEVICE;
   if (hipDeviceGetAttribute(&c->ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || c->ncu < 1)
     return LF_ERR_DEVICE;
   *out = c.release();
@@ -367,6 +369,7 @@ void lf_ctx_destroy(lf_ctx *c) {
   if (c->sink) (void)hipFree(c->sink);
   if (c->dead) (void)hipFree(c->dead);
   if (c->zero80) (void)hipFree(c->zero80);
+  if (c->toptbl) (void)hipFree(c->toptbl);
   if (c->stage) (void)hipFree(c->stage);
   if (c->limb) (void)hipFree(c->limb);
   if (c->tmp) (void)hipFree(c->tmp);

@@ -61,8 +61,9 @@
  * Data: a ring element is d u64 (AoS). d = 24 is the reference's Goldilocks
  * ring Fq[X]/(X^24 - X^12 + 1); its NTT form is 8 Fq3 slots laid out
  * [s0.c0, s0.c1, s0.c2, s1.c0, ...] exactly as the reference's in-place CRT
- * (crt.rs:53-77). d in {16, 64, 256, 1024, 4096} selects Fq[X]/(X^d + 1)
- * (no reference analogue; NTT slot k = f(psi^(2k+1)), psi = 7^((p-1)/2d)).
+ * (crt.rs:53-77). Every other supported d selects Fq[X]/(X^d + 1) (no reference
+ * analogue; NTT slot k = f(psi^(2k+1)), psi = 7^((p-1)/2d)). The supported
+ * degrees are 24, and every power of two from 16 to 4096 (lf_ring_supported).
  * Host-buffer calls take repr = LF_REPR_MONTGOMERY when the buffers are raw
  * ark-ff Fp64 limbs (zero-copy from Rust Vec<RqNTT>), LF_REPR_CANONICAL
  * otherwise. Device (lf_dev_*) calls are canonical and asynchronous on the
@@ -119,6 +120,11 @@ typedef struct {
 
 /* zkvm GoldiLocksDP (zkvm/src/ccs.rs:26-34): B = 2^15, L = 5, B_SMALL = 2, K = 15 */
 lf_params lf_goldilocks_dp(int d);
+
+/* 1 when ring degree d is supported (24, and every power of two from 16 to 4096),
+ * else 0; every other d gets LF_ERR_UNSUPPORTED_RING from the calls below. Needs
+ * no context: a host can ask before it allocates. */
+int lf_ring_supported(int d);
 
 /* ------------------------------------------------------------ context */
 int lf_ctx_create(int device, lf_ctx **out);

@@ -22,7 +22,7 @@ from ._lib import LfComb, LfFoldStepBufs, LfParams, load
 P = (1 << 64) - (1 << 32) + 1
 REPR_CANONICAL = 0
 REPR_MONTGOMERY = 1
-SUPPORTED_D = (24, 16, 64, 256, 1024, 4096)
+SUPPORTED_D = (24, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096)
 
 
 class LfError(RuntimeError):
@@ -34,6 +34,11 @@ class LfError(RuntimeError):
 def goldilocks_dp(d: int = 24) -> LfParams:
     """zkvm GoldiLocksDP (zkvm/src/ccs.rs:26-34): B=2^15, L=5, B_SMALL=2, K=15."""
     return load().lf_goldilocks_dp(d)
+
+
+def ring_supported(d: int) -> bool:
+    """lf_ring_supported: d is 24 or a power of two from 16 to 4096 (needs no Context)."""
+    return bool(load().lf_ring_supported(int(d)))
 
 
 def _u64(a) -> np.ndarray:

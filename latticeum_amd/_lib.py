@@ -87,6 +87,7 @@ class LfComb(C.Structure):
 # every function exported by include/lf.h: name -> (restype, argtypes)
 SIGNATURES = {
     "lf_goldilocks_dp": (LfParams, [I]),
+    "lf_ring_supported": (I, [I]),
     "lf_ctx_create": (I, [I, C.POINTER(VP)]),
     "lf_ctx_destroy": (None, [VP]),
     "lf_status_string": (C.c_char_p, [I]),

@@ -176,7 +176,8 @@ inline int fail(lf_ctx *c, int code, const std::string &msg) {
     if (r_ != LF_OK) return r_; \
   } while (0)
 
-inline bool ring_ok(int d) { return d == 24 || d == 16 || d == 64 || d == 256 || d == 1024 || d == 4096; }
+// 24 (Phi_72), and X^d + 1 for every power of two from 16 to 4096 (lf_ring_supported)
+inline bool ring_ok(int d) { return d == 24 || (d >= 16 && d <= 4096 && (d & (d - 1)) == 0); }
 
 inline int log2_exact(uint64_t v) {
   if (v < 2 || (v & (v - 1))) return -1;

@@ -1,7 +1,7 @@
 // kernels.hip -- hand-written gfx950 kernels for the LatticeFold commit+fold
 // hot path. Data layout in HBM: AoS ring elements, d u64 each (d = 24 for
 // Phi_72 in the reference's in-place CRT layout [s0.c0, s0.c1, s0.c2, s1.c0, ..]
-// (stark-rings crt.rs:53-77), d = 4^k for the negacyclic rings), canonical
+// (stark-rings crt.rs:53-77), d = 2^k, 16 <= d <= 4096, for the negacyclic rings), canonical
 // values. Every launcher returns hipError_t and takes the stream explicitly.
 #include <cstdlib>
 #include <cstring>
@@ -1033,6 +1033,8 @@ __global__ void __launch_bounds__(256) k_fold_phi72(const uint64_t *rho, VecPtrs
 
 static inline unsigned blocks(size_t n, int t) { return (unsigned)((n + t - 1) / t); }
 static inline unsigned grid_cap(size_t n) { return (unsigned)(n < 65536 ? n : 65536); }
+// the X^d + 1 degrees of the LDS transform's kernels (ring.hpp stockham4): one case per degree in each launcher
+#define LF_NEGA_DEGREES(X) X(16) X(32) X(64) X(128) X(256) X(512) X(1024) X(2048) X(4096)
 
 // ============================================================ Phi_72 fold in coefficient form
 // The 2K folded witnesses are digit planes, f_i = CRT(D_i) with D_i in {-1, 0, 1}^24,
@@ -1454,11 +1456,7 @@ hipError_t transform(uint64_t *data, size_t n, int d, bool fwd, const ring::Nega
                          st, data, n, tb);                                                        \
     break;
   switch (d) {
-    LF_NEGA_T(16)
-    LF_NEGA_T(64)
-    LF_NEGA_T(256)
-    LF_NEGA_T(1024)
-    LF_NEGA_T(4096)
+    LF_NEGA_DEGREES(LF_NEGA_T)
     default:
       return hipErrorInvalidValue;
   }
@@ -1500,7 +1498,7 @@ hipError_t from_w_ccs(const uint64_t *w_ccs, size_t W, int d, int lb, int L, uin
                        lb, L, f_coeff, f, fwd, inv, err);                                          \
     break;
   switch (d) {
-    LF_CASE(16) LF_CASE(64) LF_CASE(256) LF_CASE(1024) LF_CASE(4096) default : return hipErrorInvalidValue;
+    LF_NEGA_DEGREES(LF_CASE) default : return hipErrorInvalidValue;
   }
 #undef LF_CASE
   return hipGetLastError();
@@ -1526,7 +1524,7 @@ hipError_t from_f(const uint64_t *f, size_t N, int d, int lb, int L, uint64_t *f
                        f_coeff, w_ccs, inv);                                                     \
     break;
   switch (d) {
-    LF_CASE(16) LF_CASE(64) LF_CASE(256) LF_CASE(1024) LF_CASE(4096) default : return hipErrorInvalidValue;
+    LF_NEGA_DEGREES(LF_CASE) default : return hipErrorInvalidValue;
   }
 #undef LF_CASE
   return hipGetLastError();
@@ -1621,7 +1619,7 @@ hipError_t decompose_witness(const uint64_t *f_coeff, size_t N, int d, int lb, i
                        lb, L, lbs, K, f_coeff_k, f_k, w_ccs_k, fwd, err);                            \
     break;
   switch (d) {
-    LF_CASE(16) LF_CASE(64) LF_CASE(256) LF_CASE(1024) LF_CASE(4096) default : return hipErrorInvalidValue;
+    LF_NEGA_DEGREES(LF_CASE) default : return hipErrorInvalidValue;
   }
 #undef LF_CASE
   return hipGetLastError();

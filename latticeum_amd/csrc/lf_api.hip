@@ -297,6 +297,8 @@ lf_params lf_goldilocks_dp(int d) {
   return p;
 }
 
+int lf_ring_supported(int d) { return ring_ok(d) ? 1 : 0; }
+
 const char *lf_status_string(int s) {
   switch (s) {
     case LF_OK: return "ok";

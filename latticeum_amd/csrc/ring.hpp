@@ -5,9 +5,10 @@
 //    root of unity in that file is a power of two (omega_24 = 2^40, 2^192 == 1),
 //    so all twiddle products are shifts (gl::shl192);
 //    only the ICRT's KAPPA (ntt.rs:43) is a general product.
-//  * X^d + 1, d = 4^k (this project's negacyclic ring, no reference analogue):
-//    slot k = f(psi^(2k+1)), psi = 7^((p-1)/2d), natural order. Radix-4
-//    Stockham (self-sorting) DFT in LDS after a psi^j twist.
+//  * X^d + 1, d a power of two from 16 to 4096 (this project's negacyclic ring,
+//    no reference analogue): slot k = f(psi^(2k+1)), psi = 7^((p-1)/2d), natural
+//    order. Radix-4 Stockham (self-sorting) DFT in LDS after a psi^j twist, with
+//    one radix-2 pass in front when log2 d is odd.
 #pragma once
 #include "gl.hpp"
 
@@ -223,17 +224,40 @@ struct NegaTables {
   const uint64_t *midq = nullptr;  // middle factors with the j1 twist, [4][j1 32][brv5(m1) 32]
 };
 
-// Radix-4 Stockham DFT of size D over LDS buffers x -> y (ping-pong), T threads.
-// Returns the buffer holding the result. Caller has already applied the twist
-// (forward) and applies the inverse twist afterwards (inverse). The 4th root
-// omega^(D/4) = 7^((p-1)/4) = 2^48 for every D (checked when the tables are
-// built), so that factor is a shift; the inverse uses 2^-48 = 2^144.
+constexpr bool log2_odd(int D) { return D > 1 && !log2_odd(D / 2); }
+
+// Stockham DFT of size D (a power of two) over LDS buffers x -> y (ping-pong),
+// T threads. Radix-4 passes at p = 1, 4, 16, ... when D = 4^k; when D = 2 4^k
+// one radix-2 pass comes first, at p = 1, where it needs no twiddles (omega^(D/2)
+// = -1 either way), and the radix-4 passes follow at p = 2, 8, 32, .... A radix-r
+// pass over i < D/r, with k = i & (p - 1) and s = D/(r p), reads x[i + q D/r],
+// multiplies by roots[q s k] and writes y[(i - k) r + k + o p]. The pass count's
+// parity depends on D: use the returned pointer, the buffer holding the result.
+// Caller has already applied the twist (forward) and applies the inverse twist
+// afterwards (inverse). The 4th root omega^(D/4) = 7^((p-1)/4) = 2^48 for every
+// D (checked when the tables are built), so that factor is a shift; the inverse
+// uses 2^-48 = 2^144.
 template <int D, int T, bool INV>
 __device__ __forceinline__ uint64_t *stockham4(uint64_t *x, uint64_t *y, const uint64_t *roots,
                                                int tid) {
+  static_assert(D >= 16 && (D & (D - 1)) == 0, "D is a power of two");
+  static_assert((D / 4) % T == 0, "every thread does the same number of butterflies");
   constexpr int E4 = INV ? 144 : 48;
+  constexpr bool R2 = log2_odd(D);
+  if (R2) {
+#pragma unroll
+    for (int i = tid; i < D / 2; i += T) {
+      const uint64_t a0 = x[i], a1 = x[i + D / 2];
+      y[2 * i] = gl::add(a0, a1);
+      y[2 * i + 1] = gl::sub(a0, a1);
+    }
+    __syncthreads();
+    uint64_t *t = x;
+    x = y;
+    y = t;
+  }
 #pragma unroll 1
-  for (int p = 1; p < D; p <<= 2) {
+  for (int p = R2 ? 2 : 1; p < D; p <<= 2) {
     const int s = D / (4 * p);
 #pragma unroll
     for (int i = tid; i < D / 4; i += T) {

@@ -294,8 +294,11 @@ typedef struct {
   /* b_small = 2 (optional, both sides or neither): the decomposed witnesses as
    * packed digit planes. d = 24: [K][N] u64, one per element and plane (bit i =
    * coefficient i is nonzero, bit 32 + i = it is -1). d = 1024 (the fused path):
-   * N x 2 KiB, every coefficient's 16-bit sign|magnitude word, all K planes in
-   * one (the decomposition's own packed input). With fk and fk_coeff all NULL
+   * N x 2 KiB, every coefficient's 16-bit sign|magnitude word (bits 0..14 = |x|,
+   * bit 15 = x is negative; digit k = sign(x) bit_k(|x|)), all K planes in one
+   * (the decomposition's own packed input): an element is 512 u32, and word
+   * 32 q + r (q < 16, r < 32) holds coefficient r + 64 q in its low half and
+   * coefficient r + 64 q + 32 in its high half. With fk and fk_coeff all NULL
    * the planes are the decomposed witnesses' only form: the u64 rows (2 x 8 d B
    * per element and plane) are not written; lf_dev_expand_planes makes them.
    * d = 4096 (the fused path): N x K KiB, one byte per coefficient quad and plane

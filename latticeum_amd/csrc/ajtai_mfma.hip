@@ -63,6 +63,7 @@
 
 #include "frag.hpp"
 #include "kernels.hpp"
+#include "launch.hpp"
 
 namespace lfk {
 
@@ -636,7 +637,7 @@ size_t ajtai_rowsums_elems(size_t kappa, int d, int Lp) { return (Lp > 1 ? 3 : 1
 hipError_t ajtai_rowsums(const uint64_t *A, size_t kappa, size_t ncols, int d, uint64_t *kr, uint64_t *tmp,
                          hipStream_t st, int Lp) {
   const size_t n = kappa * (size_t)d, m = kappa * (size_t)mfma_dim(d);
-  const dim3 gn((unsigned)((n + 255) / 256)), gm((unsigned)((m + 255) / 256));
+  const dim3 gn(blocks(n, 256)), gm(blocks(m, 256));
   hipLaunchKernelGGL(k_rowsum, gn, dim3(256), 0, st, A, kappa, ncols, d, tmp, (size_t)0, (size_t)1);
   hipLaunchKernelGGL(k_rowsum_kr, gm, dim3(256), 0, st, tmp, kappa, d, mfma_dim(d), kr);
   if (Lp > 1) {
@@ -877,7 +878,7 @@ hipError_t ajtai_mfma_steps(const uint4 *Af, const uint64_t *kr, size_t kappa, c
     }
     if (d == 24) {
       const size_t n = (size_t)nvec * kappa * 8;
-      hipLaunchKernelGGL(k_phi72_interp, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, so.dst[s].p[0], nvec,
+      hipLaunchKernelGGL(k_phi72_interp, dim3(blocks(n, 256)), dim3(256), 0, st, so.dst[s].p[0], nvec,
                          kappa, dst[s]);
       e = hipGetLastError();
       if (e != hipSuccess) return e;

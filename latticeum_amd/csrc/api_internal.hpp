@@ -14,6 +14,7 @@
 #include "../../include/lf.h"
 #include "gl.hpp"
 #include "kernels.hpp"
+#include "launch.hpp"
 
 struct Tables {
   uint64_t *mem = nullptr;  // 4*d u64: fwd twist | fwd roots | inv twist | inv roots
@@ -176,8 +177,9 @@ inline int fail(lf_ctx *c, int code, const std::string &msg) {
     if (r_ != LF_OK) return r_; \
   } while (0)
 
-// 24 (Phi_72), and X^d + 1 for every power of two from 16 to 4096 (lf_ring_supported)
-inline bool ring_ok(int d) { return d == 24 || (d >= 16 && d <= 4096 && (d & (d - 1)) == 0); }
+// 24 (Phi_72), and X^d + 1 for the degrees the kernels are built for (launch.hpp
+// NegaDegrees: every power of two from 16 to 4096; lf_ring_supported)
+inline bool ring_ok(int d) { return d == 24 || lfk::nega_degree_ok(d); }
 
 inline int log2_exact(uint64_t v) {
   if (v < 2 || (v & (v - 1))) return -1;

@@ -119,7 +119,7 @@ int decompose_n4k_sides(lf_ctx *c, const Tables *t, lfk::FusedSides &sd, size_t 
   const bool own = !(frag && sd.smg[0]);
   // the smg scratch a d = 1024 step's coefficient fold would read may be overwritten here
   if (c->step.path == FoldPath::Coeff1024 || c->step.path == FoldPath::Coeff1024Rows) c->step = {};
-  if (own) LF_TRY(grow(c, c->smg, c->smg_elems, (size_t)sd.nside * N * (frag ? (size_t)K * 256 : 2048)));
+  if (own) LF_TRY(grow(c, c->smg, c->smg_elems, (size_t)sd.nside * N * (frag ? lfk::sm8_words(K) : 2 * lfk::SM4_WORDS)));
   LF_HIP(c, lfk::decompose_n4k(sd, N, lb, L, K, own ? reinterpret_cast<uint64_t *>(c->smg) : nullptr, t->fwd, c->d_err,
                                c->sink, c->ncu, c->cur, frag, nch));
   return LF_OK;
@@ -165,7 +165,7 @@ int fold_commit(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, int lb, int 
   const uint64_t *fc_side[2] = {b->acc_f_coeff, wi_f_coeff};
   const size_t kd = kappa * (size_t)d;
   // the fused decompositions write their digit planes straight into the MFMA operand
-  // buffer: X^1024 + 1, Phi_72 (kernels.hip) and X^4096 + 1 (kernels_n4k.hip)
+  // buffer: X^1024 + 1 (kernels_n32.hip), Phi_72 (decompose_phi72.hip) and X^4096 + 1 (kernels_n4k.hip)
   StepPlan plan = step_plan(aj, pr, lbs, t, b);
   const bool fused = plan.dec == Decomp::Fused1024, fused24 = plan.dec == Decomp::Fused24,
              fused4k = plan.dec == Decomp::Fused4k;
@@ -252,10 +252,10 @@ int fold_commit(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, int lb, int 
   } else if (fused) {
     // the packed words go straight into the caller's planes when given; fold_finish's
     // coefficient-form fold reads the digits from them
-    if (!b->planes[0]) LF_TRY(grow(c, c->smg, c->smg_elems, 2 * N * 512));
+    if (!b->planes[0]) LF_TRY(grow(c, c->smg, c->smg_elems, 2 * N * lfk::SM1024_WORDS));
     for (int s = 0; s < 2; s++)
       st.smg_side[s] = sd.smg[s] =
-          b->planes[0] ? reinterpret_cast<uint32_t *>(b->planes[s]) : c->smg + (size_t)s * N * 512;
+          b->planes[0] ? reinterpret_cast<uint32_t *>(b->planes[s]) : c->smg + (size_t)s * N * lfk::SM1024_WORDS;
     // side 1's words, when step_commit's from_w_ccs wrote them into this very buffer
     sd.prepacked = prepacked1 && prepacked1 == sd.smg[1] && wi_f_coeff == b->f_coeff ? 2 : 0;
     PhaseTimer pt(c, LF_PHASE_DECOMPOSE);  // both sides in one launch
@@ -265,14 +265,14 @@ int fold_commit(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, int lb, int 
     // b_small = 2: the digit masks for fold_finish's coefficient-form fold,
     // into the caller's planes if given, else the context's scratch
     const bool want_masks = lbs == 1;
-    if (want_masks && !b->planes[0]) LF_TRY(grow(c, c->fkeys, c->fkeys_elems, 2 * 2 * (size_t)K * N));
-    LF_TRY(grow(c, c->smg, c->smg_elems, 2 * N * 12));  // the coefficients as 16-bit sign|magnitude
+    if (want_masks && !b->planes[0]) LF_TRY(grow(c, c->fkeys, c->fkeys_elems, 2 * 2 * lfk::mask24_elems(K, N)));
+    LF_TRY(grow(c, c->smg, c->smg_elems, 2 * N * lfk::SM24_WORDS));  // the coefficients as 16-bit sign|magnitude
     if (lbs != 1) sd.dead = nullptr;  // only the wave-local b_small = 2 kernel flags the zero planes' rows
     for (int s = 0; s < 2; s++) {
-      sd.smg[s] = c->smg + (size_t)s * N * 12;
+      sd.smg[s] = c->smg + (size_t)s * N * lfk::SM24_WORDS;
       if (want_masks)
         sd.masks[s] = b->planes[s] ? reinterpret_cast<uint2 *>(b->planes[s])
-                                   : reinterpret_cast<uint2 *>(c->fkeys) + (size_t)s * K * N;
+                                   : reinterpret_cast<uint2 *>(c->fkeys) + (size_t)s * lfk::mask24_elems(K, N);
       st.masks24[s] = sd.masks[s];
     }
     PhaseTimer pt(c, LF_PHASE_DECOMPOSE);  // both sides in one launch
@@ -381,7 +381,7 @@ int fold_finish(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, int lb, int 
       return LF_OK;
     }
     // Phi_72 after the wave-local decomposition: f_0 in coefficient form from its
-    // digit masks, then f_0 = CRT and w_ccs_0 (kernels.hip k_fold_coeff_phi72); a
+    // digit masks, then f_0 = CRT and w_ccs_0 (fold.hip k_fold_coeff_phi72); a
     // rho that is not short raises `bad`, which turns that kernel off and the
     // NTT-form fold and Witness::from_f on
     case FoldPath::Masks24:
@@ -444,8 +444,8 @@ int step_commit(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, size_t W, co
     const size_t N = W * (size_t)L;
     if (step_plan(aj, pr, lbs, t, b).dec == Decomp::Fused1024 && t->inv.mid && lb <= K && aj->ncols == N &&
         (!b->planes[0]) == (!b->planes[1])) {
-      if (!b->planes[0]) LF_TRY(grow(c, c->smg, c->smg_elems, 2 * N * 512));
-      smg1 = b->planes[1] ? reinterpret_cast<uint32_t *>(b->planes[1]) : c->smg + N * 512;
+      if (!b->planes[0]) LF_TRY(grow(c, c->smg, c->smg_elems, 2 * N * lfk::SM1024_WORDS));
+      smg1 = b->planes[1] ? reinterpret_cast<uint32_t *>(b->planes[1]) : c->smg + N * lfk::SM1024_WORDS;
     }
     if (!b->w_ccs || !b->f_coeff || !b->f) return fail(c, LF_ERR_INVALID_ARG, "null step buffer");
     LF_HIP(c, lfk::from_w_ccs(b->w_ccs, W, d, lb, L, b->f_coeff, b->f, t->fwd, t->inv, c->d_err, c->cur, smg1));
@@ -566,7 +566,7 @@ int lf_dev_expand_planes(lf_ctx *c, const lf_params *pr, const uint64_t *planes,
   if (!planes && N) return fail(c, LF_ERR_INVALID_ARG, "planes is NULL");
   if (lbs != 1) return fail(c, LF_ERR_INVALID_ARG, "packed planes need b_small = 2");
   if (d == 24) {  // [K][N] digit masks
-    LF_HIP(c, lfk::expand_phi72(reinterpret_cast<const uint2 *>(planes), (size_t)K * N, fck, fk, c->cur));
+    LF_HIP(c, lfk::expand_phi72(reinterpret_cast<const uint2 *>(planes), lfk::mask24_elems(K, N), fck, fk, c->cur));
     return LF_OK;
   }
   if ((d != 1024 && d != 4096) || K > 15) return fail(c, LF_ERR_UNSUPPORTED_RING, "packed planes: d = 24, 1024 or 4096");

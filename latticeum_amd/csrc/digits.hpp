@@ -19,6 +19,10 @@ __device__ __forceinline__ int64_t signed_rep(uint64_t v) {
 __device__ __forceinline__ uint64_t from_signed(int64_t x) {
   return x < 0 ? gl::P - (uint64_t)(-x) : (uint64_t)x;
 }
+// coefficient i of a Phi_72 digit-mask pair as a field element (digitpack.hpp mask24_digit mod p)
+__device__ __forceinline__ uint64_t pw_digit(uint32_t nz, uint32_t ng, int i) {
+  return (nz >> i & 1) ? ((ng >> i & 1) ? gl::P - 1 : 1) : 0;
+}
 // one balanced digit step (balanced_decomposition/mod.rs:76-91) for b = 2^lb
 __device__ __forceinline__ int64_t bal_digit(int64_t &curr, int lb) {
   const int64_t b = (int64_t)1 << lb, bh = b >> 1;

@@ -28,9 +28,11 @@
 // on the device); otherwise the flag it raises makes these kernels return at
 // once and the NTT-form fold and Witness::from_f run instead (the same flag,
 // the other way round), with no host synchronisation.
+#include "digitpack.hpp"
 #include "digits.hpp"
 #include "frag.hpp"
 #include "kernels.hpp"
+#include "launch.hpp"
 #include "ntt32.hpp"
 
 namespace lfk {
@@ -51,8 +53,7 @@ __device__ __forceinline__ uint32_t spread8(uint32_t x) {
 // keys[(col K + k) 64 + h 32 + q] byte i = key of quad p = 8q + 4h + i (its
 // coefficients 4p .. 4p + 3) in plane k: bit m = bit k of |x_(4p+m)|, bit 4 + m
 // = its sign. From the fused decomposition's packed coefficients
-// (k_pack_sm: smg[(col 16 + qq) 32 + rr] = sm(x[rr + 64 qq]) | sm(x[rr + 64 qq + 32]) << 16,
-// sm = 15-bit magnitude | sign << 15). One thread per (col, h, 4 consecutive q):
+// (digitpack.hpp, d = 1024). One thread per (col, h, 4 consecutive q):
 // 128 B in, one 16-B row piece per plane out.
 // nz[col] (when given): bit k = plane k of the column has a nonzero digit (the 16
 // threads of a column are 16 consecutive lanes of one wave: OR by shuffles)
@@ -67,7 +68,7 @@ __global__ void __launch_bounds__(256) k_pack_keys(const uint32_t *smg, size_t n
   uint32_t w[2][16];
 #pragma unroll
   for (int a = 0; a < 2; a++) {
-    const uint4 *src = reinterpret_cast<const uint4 *>(smg + col * 512 + (q0 / 2 + a) * 32 + 16 * h);
+    const uint4 *src = reinterpret_cast<const uint4 *>(smg + sm1024_word(col, q0 / 2 + a, 16 * h));
 #pragma unroll
     for (int v = 0; v < 4; v++) {
       const uint4 x = src[v];
@@ -83,7 +84,7 @@ __global__ void __launch_bounds__(256) k_pack_keys(const uint32_t *smg, size_t n
     for (int a = 0; a < 2; a++)
 #pragma unroll
       for (int i = 0; i < 16; i++) m |= w[a][i] | (w[a][i] >> 16);
-    m &= 0x7FFFu;
+    m &= SM16_MAG;
 #pragma unroll
     for (int o = 1; o < 16; o <<= 1) m |= __shfl_xor(m, o);
     if (live_t && (t & 15) == 0) nz[col] = m;
@@ -353,7 +354,7 @@ int fold_coeff_splits(size_t N, int K, int ncu) {
 hipError_t fold_keys(const uint32_t *smg, size_t ncol, int K, uint32_t *keys, hipStream_t st, uint32_t *nz) {
   if (K < 1 || K > 15) return hipErrorInvalidValue;
   if (!ncol) return hipSuccess;
-  hipLaunchKernelGGL(k_pack_keys, dim3((unsigned)((ncol * 16 + 255) / 256)), dim3(256), 0, st, smg, ncol, K, keys,
+  hipLaunchKernelGGL(k_pack_keys, dim3(blocks(ncol * 16, 256)), dim3(256), 0, st, smg, ncol, K, keys,
                      nz);
   return hipGetLastError();
 }
@@ -380,7 +381,7 @@ hipError_t fold_coeff(const uint32_t *keys, const uint8_t *tab, const int *bad, 
                      K, f0c, ks_n, part, fbv, L, nz);
   if (ks_n > 1) {
     const size_t n = N * FD;
-    hipLaunchKernelGGL(k_fold_coeff_sum, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, st, part, ks_n, n, bad,
+    hipLaunchKernelGGL(k_fold_coeff_sum, dim3(blocks(n / 4, 256)), dim3(256), 0, st, part, ks_n, n, bad,
                        f0c);
   }
   return hipGetLastError();

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
 #define LF_HD __host__ __device__ __forceinline__
 #else
 #define LF_HD inline

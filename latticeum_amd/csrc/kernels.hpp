@@ -1,9 +1,10 @@
-// kernels.hpp -- launcher declarations for kernels.hip (internal to the library).
+// kernels.hpp -- the launcher declarations of every kernel file (internal to the library).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
+#include "digitpack.hpp"
 #include "fragpos.hpp"
 #include "ring.hpp"
 
@@ -41,13 +42,15 @@ struct StepOps {
   const uint4 *zero80 = nullptr;  // 32 operand pieces of 0x80 bytes (the offset form of 0) for dead units
 };
 
+// ---------------------------------------------------------------- transforms, slot product, Montgomery edge (transform.hip)
 hipError_t transform(uint64_t *data, size_t n, int d, bool fwd, const ring::NegaTables &tb,
                      hipStream_t st);
 hipError_t slot_mul(const uint64_t *a, const uint64_t *b, uint64_t *out, size_t n, int d,
                     hipStream_t st);
 hipError_t mont(uint64_t *x, size_t n, bool to, hipStream_t st);
+// ---------------------------------------------------------------- witness conversions, generic forms (transform.hip)
 // smg (d = 1024 only, may be null): also write the digits as the fused
-// decomposition's packed sign|magnitude words ([W L][512] u32, k_pack_sm's layout),
+// decomposition's packed sign|magnitude words (digitpack.hpp, d = 1024),
 // so that launch need not re-read f_coeff (the digits fit 15 bits when lb <= 15)
 hipError_t from_w_ccs(const uint64_t *w_ccs, size_t W, int d, int lb, int L, uint64_t *f_coeff,
                       uint64_t *f, const ring::NegaTables &fwd, const ring::NegaTables &inv, int *err,
@@ -61,6 +64,7 @@ hipError_t decompose_witness(const uint64_t *f_coeff, size_t N, int d, int lb, i
                              uint64_t *f_coeff_k, uint64_t *f_k, uint64_t *w_ccs_k,
                              const ring::NegaTables &fwd, int *err, hipStream_t st, uint4 *frag = nullptr,
                              int nch = 0, int row0 = 0);
+// ---------------------------------------------------------------- VALU Ajtai and its split sums (ajtai.hip); y_0 / cm_0 (fold.hip)
 int ajtai_nsplit(size_t ncols, int d, int nvec);
 size_t ajtai_partial_elems(size_t kappa, size_t ncols, int d, int nvec);
 hipError_t ajtai_commit(const uint64_t *A, size_t kappa, size_t ncols, int d, const VecPtrs &fv,
@@ -68,17 +72,22 @@ hipError_t ajtai_commit(const uint64_t *A, size_t kappa, size_t ncols, int d, co
                         hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 hipError_t commit_y0(const uint64_t *cm, uint64_t *y, size_t kappa, int d, int lbs, int K,
                      hipStream_t st);
+// the NTT-form linear fold (fold.hip)
 hipError_t fold(const uint64_t *rho, const VecPtrs &x, int nwit, size_t n, int d, uint64_t *out,
                 hipStream_t st, const int *run_if = nullptr);
+// width-16 Poseidon2 (poseidon2.hip)
 hipError_t p2_permute(uint64_t *states, size_t n, hipStream_t st, int rounds = 30);
+// synthetic inputs, cross-rank sums and the RCCL limb transport (util.hip)
 hipError_t fill_uniform(uint64_t *out, size_t n, uint64_t seed, hipStream_t st);
 hipError_t modp_sum(const uint64_t *in, int nparts, size_t len, uint64_t *out, hipStream_t st);
 
-// rot_lin_combination: rho_coeff [n][d] (canonical), theta [n][tau d] (tau = 3 for d = 24, else 1) -> v0 [tau d]
+// rot_lin_combination (fold.hip): rho_coeff [n][d] (canonical), theta [n][tau d] (tau = 3 for d = 24, else 1) -> v0 [tau d]
 hipError_t rot_lin(const uint64_t *rho_coeff, const uint64_t *theta, int n, int d, uint64_t *v0, hipStream_t st);
+// util.hip
 hipError_t limb_split(const uint64_t *x, size_t n, uint64_t *lo, uint64_t *hi, hipStream_t st);
 hipError_t limb_join(const uint64_t *lo, const uint64_t *hi, size_t n, uint64_t *out, hipStream_t st);
 
+// ajtai.hip
 hipError_t sum_planes(const uint64_t *partial, int nsplit, size_t len, uint64_t *out, hipStream_t st);
 // out.p[v][r] = sum_s partial[s][v][r] for nvec vectors of len u64
 hipError_t sum_planes_to(const uint64_t *partial, int nsplit, size_t len, int nvec, const OutPtrs &out,
@@ -92,7 +101,8 @@ hipError_t sum_planes_to(const uint64_t *partial, int nsplit, size_t len, int nv
 hipError_t y0_cm0(const uint64_t *cm0s, uint64_t *cm1s, uint64_t *y0, uint64_t *y1, const uint64_t *rho,
                   size_t kappa, int d, int lbs, int K, uint64_t *cm0, hipStream_t st, bool cm1_out = false);
 
-// i8-MFMA Ajtai (ajtai_mfma.hip): negacyclic rings and Phi_72, nvec <= 32,
+// ---------------------------------------------------------------- i8-MFMA Ajtai (ajtai_mfma.hip)
+// i8-MFMA Ajtai: negacyclic rings and Phi_72, nvec <= 32,
 // kappa <= 32 LF_MAX_KTILES: A is stored as mfma_ktiles(kappa) tiles of 32 rows,
 // frag_elems() uint4 each.
 // Column (contraction) order: 16-column units (G, l) = limb l of groups
@@ -145,7 +155,7 @@ hipError_t ajtai_mfma_steps(const uint4 *Af, const uint64_t *kr, size_t kappa, c
                             hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, const DeadUnits *dead = nullptr,
                             const uint4 *zero80 = nullptr, uint32_t *toptbl = nullptr);
 
-// d = 1024 kernels on the register-resident 32 x 32 NTT (kernels_n32.hip)
+// ---------------------------------------------------------------- d = 1024 on the register-resident 32 x 32 NTT (kernels_n32.hip)
 // W below which from_w_ccs / from_f run one half-wave per (element, limb)
 size_t witness_split_w();
 // data = transform(src), in place when src is null
@@ -172,8 +182,8 @@ struct FusedSides {
   int nside;
   int row_p0[2] = {-1, -1};                      // operand row of plane 0, or -1 (not written)
   uint2 *masks[2] = {nullptr, nullptr};          // d = 24, b_small = 2: digit masks [K][N] (nonzero, negative), or null
-  uint32_t *smg[2] = {nullptr, nullptr};         // packed sign|magnitude words: d = 1024 fused [N][512], d = 24 [N][12];
-                                                 // d = 4096 fused: [N][K][256] bytes (nibble | signs << 4)
+  uint32_t *smg[2] = {nullptr, nullptr};         // the packed digits (digitpack.hpp): d = 1024 fused and d = 24 the
+                                                 // sign|magnitude words, d = 4096 fused the digit bytes
   uint8_t *dead = nullptr;                       // d = 1024 fused: dead-unit flags of the rows written (DeadUnits)
   int prepacked = 0;                             // d = 1024 fused: bit s = side s's smg is already written
                                                  // (from_w_ccs wrote it; only side 1 may be)
@@ -191,7 +201,8 @@ hipError_t fold_frag(const uint4 *frag, const FragGeom &g, const FoldRows &fr, c
 hipError_t decompose_fused(const FusedSides &sd, size_t N, int lb, int L, int K, const ring::NegaTables &fwd, uint4 *frag, int nch, int *err, uint64_t *sink, int ncu,
                            hipStream_t st);
 
-// f_0 in coefficient form on the i8 matrix cores (fold_coeff.hip), X^1024 + 1, b_small = 2:
+// ---------------------------------------------------------------- coefficient-form fold, d = 1024 (fold_coeff.hip)
+// f_0 in coefficient form on the i8 matrix cores, X^1024 + 1, b_small = 2:
 // keys [ncol = nside N][K][64] u32 from decompose_fused's packed coefficients (smg);
 // rho (nw = 2K NTT elements) -> rc (nw 1024 u64 scratch, its coefficients) -> tab
 // [nw][FOLD_RT] bytes, *bad = 1 if a coefficient is outside [-127, 127];
@@ -227,6 +238,7 @@ hipError_t from_fcoeff_n32(uint64_t *f_coeff, size_t W, int lb, int L, uint64_t 
                            const ring::NegaTables &fwd, const int *gate, hipStream_t st,
                            const ring::NegaTables *inv = nullptr);
 
+// ---------------------------------------------------------------- Phi_72 decomposition (decompose_phi72.hip)
 // d = 24: both sides of a fold step in one launch (blockIdx.z = side); frag as decompose_witness
 // *masks_written: whether the launch filled sd.masks (the wave-local kernel does);
 // *dead_written: whether it left zero units unwritten and flagged them in sd.dead
@@ -234,6 +246,7 @@ hipError_t from_fcoeff_n32(uint64_t *f_coeff, size_t W, int lb, int L, uint64_t 
 hipError_t decompose_phi72_sides(const FusedSides &sd, size_t N, int lb, int L, int lbs, int K, int *err,
                                  uint4 *frag, int nch, hipStream_t st, bool *masks_written = nullptr,
                                  bool *dead_written = nullptr);
+// ---------------------------------------------------------------- Phi_72 coefficient-form fold (fold.hip)
 // f_0 in coefficient form from the decomposition's digit masks (d = 24, b_small = 2):
 // rho (2K NTT elements) -> rc [2K][25] packed 16-bit coefficient pairs, *bad = 1 if
 // one is outside [-32, 32]; unless *bad: f0_coeff = sum_i rho_i * D_i, f0 = CRT(f0_coeff),
@@ -246,11 +259,12 @@ hipError_t fold_phi72_masks(const uint2 *masks0, const uint2 *masks1, const uint
                             uint64_t *f0, const int *run_if, hipStream_t st);
 // packed Phi_72 planes (n elements) -> f_coeff (digits mod p) and / or f = CRT(f_coeff)
 hipError_t expand_phi72(const uint2 *planes, size_t n, uint64_t *fc, uint64_t *f, hipStream_t st);
-// d = 1024: the fused decomposition's packed sign|magnitude words of N elements -> f_coeff_k [K][N]
+// d = 1024 (kernels_n32.hip): the fused decomposition's packed sign|magnitude words of N elements -> f_coeff_k [K][N]
 hipError_t expand_sm(const uint32_t *smg, size_t N, int K, uint64_t *fck, hipStream_t st);
-// d = 4096: the fused decomposition's packed bytes (N K 256 words) -> f_coeff_k [K][N][4096]
+// d = 4096 (kernels_n4k.hip): the fused decomposition's digit bytes -> f_coeff_k [K][N][4096]
 hipError_t expand_sm8(const uint32_t *sm8, size_t N, int K, uint64_t *fck, hipStream_t st);
-// d = 4096, b_small = 2 (kernels_n4k.hip): sm4 holds nside N 1024 packed words; sink 4096 words.
+// ---------------------------------------------------------------- d = 4096 on the quarter transforms (kernels_n4k.hip)
+// d = 4096, b_small = 2: sm4 holds nside N SM4_WORDS Morton words (digitpack.hpp); sink 4096 words.
 // With frag (a scheme whose geometry has Lp = L and qperm), planes k >= 1 are also
 // written as operand rows row0[side] + k - 1, as decompose_fused does for d = 1024.
 hipError_t decompose_n4k(const FusedSides &sd, size_t N, int lb, int L, int K, uint64_t *sm4,

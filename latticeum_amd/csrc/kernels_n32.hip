@@ -3,9 +3,11 @@
 // one group of L elements (decompose, from_f); waves never synchronise with
 // each other and there is no s_barrier on this path. Every global access is a
 // 256-B row per half-wave (lane r touches x[r + 32 k]).
+#include "digitpack.hpp"
 #include "digits.hpp"
 #include "frag.hpp"
 #include "kernels.hpp"
+#include "launch.hpp"
 #include "ntt32.hpp"
 
 namespace lfk {
@@ -86,17 +88,13 @@ __device__ __forceinline__ void inverse_gmid(uint64_t *v, const uint64_t *mid_ig
 // The inverse middle factors read from global (L1-resident 8 KiB table),
 // no next-element prefetch, so two blocks (8 waves) fit a CU: 0.71 -> 0.52 ms at
 // W = 16 384 against the LDS-table, prefetching form (one block per CU)
-// the fused decomposition's packed words of one limb row (k_pack_sm's layout:
-// word (q, r) = sm(x[r + 64 q]) | sm(x[r + 64 q + 32]) << 16, sm = 15-bit magnitude |
-// sign << 15) straight from the digits this lane holds (x[r + 32 k] = d[k])
-__device__ __forceinline__ uint32_t sm16(int64_t d) {
-  return (uint32_t)(d < 0 ? -d : d) | (d < 0 ? 0x8000u : 0u);
-}
-// (from the field elements, so no digit array stays live beside the transform's registers)
-__device__ __forceinline__ void store_sm_row(const uint64_t *v, uint32_t *row, int r) {
+// the fused decomposition's packed words of element col (digitpack.hpp, d = 1024)
+// straight from the digits this lane holds (x[r + 32 k] = v[k]; from the field
+// elements, so no digit array stays live beside the transform's registers)
+__device__ __forceinline__ void store_sm_row(const uint64_t *v, uint32_t *smg, size_t col, int r) {
 #pragma unroll
   for (int q = 0; q < 16; q++)
-    row[q * 32 + r] = sm16(signed_rep(v[2 * q])) | (sm16(signed_rep(v[2 * q + 1])) << 16);
+    smg[sm1024_word(col, q, r)] = sign_mag16(signed_rep(v[2 * q])) | (sign_mag16(signed_rep(v[2 * q + 1])) << 16);
 }
 // smg (may be null): the digits' packed words too (from_w_ccs's comment in kernels.hpp)
 __global__ void __launch_bounds__(256, 2) k_from_w_ccs_n32(const uint64_t *w_ccs, size_t W, int lb, int L,
@@ -126,7 +124,7 @@ __global__ void __launch_bounds__(256, 2) k_from_w_ccs_n32(const uint64_t *w_ccs
         v[k] = from_signed(bal_digit(cur[k], lb));
         if (ok) oc[32 * k] = v[k];
       }
-      if (smg && ok) store_sm_row(v, smg + (j * L + l) * 512, x.r);
+      if (smg && ok) store_sm_row(v, smg, j * L + l, x.r);
       n32::forward(v, mid_f, x.lds, x.r);
       if (ok) {
         uint64_t *of = f + (j * L + l) * D + x.r;
@@ -303,7 +301,7 @@ __global__ void __launch_bounds__(256) k_from_w_ccs_digits(const uint64_t *w_ccs
         dv[k] = from_signed(bal_digit(cur[k], lb));
         if (ok) oc[32 * k] = dv[k];
       }
-      if (smg && ok) store_sm_row(dv, smg + (j * L + l) * 512, x.r);
+      if (smg && ok) store_sm_row(dv, smg, j * L + l, x.r);
     }
     bool bad = false;
 #pragma unroll
@@ -475,11 +473,8 @@ __global__ void __launch_bounds__(256, 1) k_decompose_n32(const uint64_t *f_coef
 #pragma unroll
       for (int k = 0; k < 32; k += 2) {
         const int64_t a = signed_rep(raw[k]), c = signed_rep(raw[k + 1]);
-        const uint64_t ma = a < 0 ? (uint64_t)(-a) : (uint64_t)a, mc = c < 0 ? (uint64_t)(-c) : (uint64_t)c;
-        bad |= (ma >> K) != 0 || (mc >> K) != 0;
-        const uint32_t ea = (uint32_t)(ma & 0x7FFF) | (a < 0 ? 0x8000u : 0u);
-        const uint32_t ec = (uint32_t)(mc & 0x7FFF) | (c < 0 ? 0x8000u : 0u);
-        sm[l][k >> 1][lane] = ea | (ec << 16);
+        bad |= sm16_overflow(a, K) || sm16_overflow(c, K);
+        sm[l][k >> 1][lane] = sign_mag16(a) | (sign_mag16(c) << 16);
       }
     }
     if (ok && bad) raise(err, 1);
@@ -496,9 +491,7 @@ __global__ void __launch_bounds__(256, 1) k_decompose_n32(const uint64_t *f_coef
           const uint32_t w = sm[l][q][lane];
 #pragma unroll
           for (int t = 0; t < 2; t++) {
-            const uint32_t hw = w >> (16 * t);
-            const int32_t bit = (hw >> kb) & 1;
-            dg[2 * q + t] = (hw & 0x8000) ? -bit : bit;
+            dg[2 * q + t] = sm16_digit(w >> (16 * t), kb);
           }
         }
         if (ok) {
@@ -543,9 +536,8 @@ __global__ void __launch_bounds__(256, 1) k_decompose_n32(const uint64_t *f_coef
 // orders the previous unit's reads before the new writes), and each thread
 // emits two slots' 128-byte operand pieces.
 //
-// The group's coefficients come pre-packed as 16-bit sign|magnitude
-// (k_pack_sm: smg[(col 16 + q) 32 + r] = x[r + 32(2q)] | x[r + 32(2q+1)] << 16),
-// read back per (k, l), one plane ahead.
+// The group's coefficients come pre-packed as sign|magnitude words (k_pack_sm;
+// digitpack.hpp, d = 1024), read back per (k, l), one plane ahead.
 constexpr int FD_WAVES = 8;
 constexpr int FD_SROW = 17;  // staging row stride in u64 (16 columns + pad: conflict-free)
 constexpr int FD_S_U64 = D * FD_SROW;
@@ -554,17 +546,16 @@ constexpr int FD_S_U64 = D * FD_SROW;
 // one 16-B store out
 __device__ __forceinline__ uint32_t pack_sm1(uint64_t x, int K, bool &bad) {
   const int64_t a = signed_rep(x);
-  const uint64_t m = a < 0 ? (uint64_t)(-a) : (uint64_t)a;
-  bad |= (m >> K) != 0;
-  return (uint32_t)(m & 0x7FFF) | (a < 0 ? 0x8000u : 0u);
+  bad |= sm16_overflow(a, K);
+  return sign_mag16(a);
 }
 __global__ void k_pack_sm(FusedSides sd, size_t N, int K, int *err) {
   const size_t t0 = 4 * (blockIdx.x * (size_t)blockDim.x + threadIdx.x);  // (side, col, q, r..r+3)
-  if (t0 >= sd.nside * N * 512) return;
-  const int side = t0 >= N * 512;
+  if (t0 >= sd.nside * N * SM1024_WORDS) return;
+  const int side = t0 >= N * SM1024_WORDS;
   const uint64_t *f_coeff = sd.f_coeff[side];
-  const size_t col = (t0 >> 9) - side * N;
-  const int q = (t0 >> 5) & 15, r = t0 & 31;
+  const size_t col = t0 / SM1024_WORDS - side * N;
+  const int q = (t0 >> 5) & 15, r = t0 & 31;  // t0 = side N 512 + sm1024_word(col, q, r)
   const ulonglong2 *x = reinterpret_cast<const ulonglong2 *>(f_coeff + col * D + r + 64 * q);
   const ulonglong2 a0 = x[0], a1 = x[1], c0 = x[16], c1 = x[17];
   bool bad = false;
@@ -574,7 +565,7 @@ __global__ void k_pack_sm(FusedSides sd, size_t N, int K, int *err) {
   o.z = pack_sm1(a1.x, K, bad) | (pack_sm1(c1.x, K, bad) << 16);
   o.w = pack_sm1(a1.y, K, bad) | (pack_sm1(c1.y, K, bad) << 16);
   if (bad) raise(err, 1);
-  *reinterpret_cast<uint4 *>(sd.smg[side] + (t0 - side * N * 512)) = o;
+  *reinterpret_cast<uint4 *>(sd.smg[side] + sm1024_word(col, q, r)) = o;
 }
 
 // Stage 1 of the digit planes' NTT on the matrix cores: for one element,
@@ -589,8 +580,8 @@ __global__ void k_pack_sm(FusedSides sd, size_t N, int K, int *err) {
 // does both of its halves' elements (16 products), so the transpose into the
 // second stage's layout stays inside the wave's own LDS tiles.
 __device__ __forceinline__ v4i mx_digits(const uint32_t *w8, int kb) {
-  // words q = 8 h + i of one element: x[r + 32 (2q)] | x[r + 32 (2q + 1)] << 16 (15-bit
-  // magnitude | sign << 15); byte j of the result = digit kb of x[r + 32 (16 h + j)] in {0, 1, -1}
+  // words q = 8 h + i of one element (digitpack.hpp, d = 1024: a bit trick on whole words, two
+  // sm16_digit per word); byte j of the result = digit kb of x[r + 32 (16 h + j)] in {0, 1, -1}
   v4i b;
 #pragma unroll
   for (int p = 0; p < 4; p++) {
@@ -692,7 +683,7 @@ __global__ void __launch_bounds__(512, 1) k_decompose_fused(size_t N, int L, int
     const size_t gg = ok ? g : 0;
     // words q = 8 h .. 8 h + 7 of both of the wave's elements (groups 16 B + 2 wib + e; past W: group 0)
     const size_t ge0 = 16 * B + 2 * wib < W ? 16 * B + 2 * wib : 0, ge1 = 16 * B + 2 * wib + 1 < W ? 16 * B + 2 * wib + 1 : 0;
-    auto word = [&](int q, int l) { return smg[(((q < 8 ? ge0 : ge1) * L + l) * 16 + 8 * h + (q & 7)) * 32 + r]; };
+    auto word = [&](int q, int l) { return smg[sm1024_word((q < 8 ? ge0 : ge1) * L + l, 8 * h + (q & 7), r)]; };
     uint32_t wn[16];  // next limb's packed words
 #pragma unroll
     for (int q = 0; q < 16; q++) wn[q] = word(q, L - 1);
@@ -811,10 +802,7 @@ __global__ void k_expand_sm(const uint32_t *smg, size_t N, int K, uint64_t *fck)
        t += (size_t)gridDim.x * blockDim.x) {
     const int j = (int)(t % D), k = (int)(t / ((size_t)N * D));
     const size_t col = (t / D) % N;
-    const int r = j & 31, jt = j >> 5, q = jt >> 1, h = jt & 1;
-    const uint32_t hw = (smg[(col * 16 + q) * 32 + r] >> (16 * h)) & 0xFFFFu;
-    const int64_t bit = (hw >> k) & 1;
-    fck[t] = from_signed((hw & 0x8000u) ? -bit : bit);
+    fck[t] = from_signed(sm1024_digit(smg, col, j, k));
   }
 }
 
@@ -822,8 +810,7 @@ hipError_t expand_sm(const uint32_t *smg, size_t N, int K, uint64_t *fck, hipStr
   if (!N) return hipSuccess;
   if (K < 1 || K > 15) return hipErrorInvalidValue;
   const size_t n = (size_t)K * N * D;
-  const size_t nb = (n + 255) / 256;
-  hipLaunchKernelGGL(k_expand_sm, dim3((unsigned)(nb < 65536 ? nb : 65536)), dim3(256), 0, st, smg, N, K, fck);
+  hipLaunchKernelGGL(k_expand_sm, dim3(grid_cap(blocks(n, 256))), dim3(256), 0, st, smg, N, K, fck);
   return hipGetLastError();
 }
 
@@ -838,8 +825,8 @@ hipError_t decompose_fused(const FusedSides &sd, size_t N, int lb, int L, int K,
   FusedSides sp = sd;
   if (sd.prepacked & 2) sp.nside = 1;  // side 0 only
   {
-    const size_t words = sp.nside * N * 512;
-    hipLaunchKernelGGL(k_pack_sm, dim3((unsigned)((words / 4 + 255) / 256)), dim3(256), 0, st, sp, N, K, err);
+    const size_t words = sp.nside * N * SM1024_WORDS;
+    hipLaunchKernelGGL(k_pack_sm, dim3(blocks(words / 4, 256)), dim3(256), 0, st, sp, N, K, err);
   }
   // one 8-wave block per CU (LDS-bound); ntask = nblk K tasks spread evenly
   const size_t ntask = (N / L + 15) / 16 * (size_t)K * sd.nside;

@@ -12,9 +12,11 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "digitpack.hpp"
 #include "digits.hpp"
 #include "frag.hpp"
 #include "kernels.hpp"
+#include "launch.hpp"
 #include "ntt32.hpp"
 
 namespace lfk {
@@ -23,37 +25,27 @@ namespace {
 constexpr int D4 = 4096, Q4 = 1024;
 constexpr int WPB4 = 8;  // two work-item pairs x four quarters; one block per CU (LDS)
 
-// bit t of a 16-bit value -> bit 4 t (Morton spread for four interleaved values)
-__device__ __forceinline__ uint64_t spread4(uint32_t v) {
-  uint64_t x = v & 0xFFFFu;
-  x = (x | (x << 24)) & 0x000000FF000000FFull;
-  x = (x | (x << 12)) & 0x000F000F000F000Full;
-  x = (x | (x << 6)) & 0x0303030303030303ull;
-  x = (x | (x << 3)) & 0x1111111111111111ull;
-  return x;
-}
-__device__ __forceinline__ uint32_t sign_mag16(uint64_t x, int K, bool &bad) {
+// a field element's sign|magnitude word, with the range check |x| < 2^K
+__device__ __forceinline__ uint32_t pack_sm1(uint64_t x, int K, bool &bad) {
   const int64_t a = signed_rep(x);
-  const uint64_t m = a < 0 ? (uint64_t)(-a) : (uint64_t)a;
-  bad |= (m >> K) != 0;
-  return (uint32_t)(m & 0x7FFF) | (a < 0 ? 0x8000u : 0u);
+  bad |= sm16_overflow(a, K);
+  return sign_mag16(a);
 }
 }  // namespace
 
 // ---------------------------------------------------------------- decompose_witness, d = 4096
-// The coefficients of element e at a, a + 1024, a + 2048, a + 3072 as one word:
-// magnitude bit t of quarter b at bit 4 t + b, the sign of quarter b at bit 60 + b
-// (K <= 15), so digit plane k of all four is the nibble at 4 k and one shift.
+// The coefficients of element e at a, a + 1024, a + 2048, a + 3072 as one Morton word
+// (digitpack.hpp, d = 4096): digit plane k of all four is the nibble at 4 k and one shift.
 __global__ void k_pack_sm4(FusedSides sd, size_t N, int K, uint64_t *sm4, int *err) {
   const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;  // (side, element, a)
-  if (t >= sd.nside * N * Q4) return;
-  const int side = t >= N * Q4;
-  const size_t ea = t - side * N * Q4;
+  if (t >= sd.nside * N * SM4_WORDS) return;
+  const int side = t >= N * SM4_WORDS;
+  const size_t ea = t - side * N * SM4_WORDS;  // sm4_word(e, a)
   const uint64_t *x = sd.f_coeff[side] + (ea >> 10) * D4 + (ea & (Q4 - 1));
   bool bad = false;
   uint64_t w = 0;
 #pragma unroll
-  for (int b = 0; b < 4; b++) w |= spread4(sign_mag16(x[b * Q4], K, bad)) << b;
+  for (int b = 0; b < 4; b++) w |= sm4_put(pack_sm1(x[b * Q4], K, bad), b);
   if (bad) raise(err, 1);
   sm4[t] = w;
 }
@@ -71,6 +63,8 @@ __device__ __forceinline__ void quarter_ntt(const uint64_t *words, int kb, int m
 #pragma unroll
   for (int k = 0; k < 32; k++) {
     const uint64_t w = v[k];
+    // sm4_nibble(w, kb), sm4_signs(w) and sm8_make(nib, sg) of digitpack.hpp, spelled out:
+    // through the helpers this loop is scheduled differently from the measured form
     const uint32_t nib = (uint32_t)(w >> (4 * kb)) & 15u, sg = (uint32_t)(w >> 60);
     const uint32_t bit = (nib >> m0) & 1u, neg = (sg >> m0) & 1u;
     // this quarter's digit: 0, 1 or p - 1 = 0xFFFFFFFF00000000
@@ -132,12 +126,12 @@ __global__ void __launch_bounds__(512, 1) k_decompose_n4k(const uint64_t *sm4_al
     const size_t gt = tt / K;
     const int side = gt >= W;
     const size_t g = gt - side * W;
-    const uint64_t *sm4 = sm4_all + side * N * Q4;
+    const uint64_t *sm4 = sm4_all + side * N * SM4_WORDS;
     uint64_t acc[32];
     for (int l = L - 1; l >= 0; l--) {
       const size_t e = (size_t)kb * N + g * L + l;
       uint64_t v[32];
-      quarter_ntt<false>(sm4 + (g * L + l) * Q4 + r, kb, m0, zt, tw,
+      quarter_ntt<false>(sm4 + sm4_word(g * L + l, r), kb, m0, zt, tw,
                          (ok ? sd.f_coeff_k[side] + e * D4 + m0 * Q4 : sink) + r, mid_f, T, r, v);
       uint64_t *of = (ok ? sd.f_k[side] + e * D4 : sink) + m0 + 4 * r;
 #pragma unroll
@@ -172,13 +166,13 @@ constexpr int FQ_T_U64 = FQ_WAVES * n32::WAVE_U64;
 constexpr int FQ_S_U64 = Q4 * FQ_SROW;
 constexpr int FQ_LDS_U64 = FQ_T_U64 > FQ_S_U64 ? FQ_T_U64 : FQ_S_U64;
 
-// byte (element e, plane kb, lane r, k) at ((e K + kb) 32 + r) 32 + k; one
-// thread per (side, e, r, j) packs k = 4 j .. 4 j + 3 (one word per plane)
+// the digit bytes (digitpack.hpp, d = 4096): one thread per (side, e, r, j) packs
+// the bytes k = 4 j .. 4 j + 3 of lane r (one word per plane)
 __global__ void k_pack_sm8(FusedSides sd, size_t N, int K, int *err) {
   const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;  // (side, element, r, j)
-  if (t >= sd.nside * N * 256) return;
-  const int side = t >= N * 256;
-  const size_t erj = t - side * N * 256, e = erj >> 8;
+  if (t >= sd.nside * N * SM8_PLANE_WORDS) return;
+  const int side = t >= N * SM8_PLANE_WORDS;
+  const size_t erj = t - side * N * SM8_PLANE_WORDS, e = erj / SM8_PLANE_WORDS;
   const int r = (int)((erj >> 3) & 31), j = (int)(erj & 7);
   const uint64_t *x = sd.f_coeff[side] + e * D4 + r + 128 * j;
   uint64_t w[4];
@@ -187,16 +181,14 @@ __global__ void k_pack_sm8(FusedSides sd, size_t N, int K, int *err) {
   for (int k = 0; k < 4; k++) {
     w[k] = 0;
 #pragma unroll
-    for (int b = 0; b < 4; b++) w[k] |= spread4(sign_mag16(x[32 * k + b * Q4], K, bad)) << b;
+    for (int b = 0; b < 4; b++) w[k] |= sm4_put(pack_sm1(x[32 * k + b * Q4], K, bad), b);
   }
   if (bad) raise(err, 1);
-  uint32_t *o = sd.smg[side] + (e * K * 32 + r) * 8 + j;
   for (int kb = 0; kb < K; kb++) {
     uint32_t q = 0;
 #pragma unroll
-    for (int k = 0; k < 4; k++)
-      q |= (((uint32_t)(w[k] >> (4 * kb)) & 15u) | ((uint32_t)(w[k] >> 60) << 4)) << (8 * k);
-    o[kb * 256] = q;
+    for (int k = 0; k < 4; k++) q |= sm8_make(sm4_nibble(w[k], kb), sm4_signs(w[k])) << (8 * k);
+    sd.smg[side][sm8_word(e, K, kb, r, j)] = q;
   }
 }
 
@@ -232,7 +224,7 @@ __global__ void __launch_bounds__(512, 1) k_decompose_n4k_fused(size_t N, int L,
     const size_t gg = ok ? g : 0;
     // this lane's 32 bytes of limb l: 8 words
     const uint32_t *sm8 = sd.smg[side];
-    auto bytes_of = [&](int l) { return sm8 + (((gg * L + l) * K + kb) * 32 + r) * 8; };
+    auto bytes_of = [&](int l) { return sm8 + sm8_word(gg * L + l, K, kb, r, 0); };
     // f_coeff_k / f_k rows only when the caller keeps them (side-uniform); packed
     // steps keep the bytes above as the decomposed witnesses' only form
     uint64_t *fck = sd.f_coeff_k[side], *fk = sd.f_k[side];
@@ -435,7 +427,7 @@ __global__ void __launch_bounds__(512, 1) k_decompose_n4k_mx(size_t N, int L, in
     const size_t ge1 = 16 * B + 2 * wib + 1 < W ? 16 * B + 2 * wib + 1 : 0;
     const uint32_t *sm8 = sd.smg[side];
     auto bytes_of = [&](size_t ge, int l) {
-      return reinterpret_cast<const uint4 *>(sm8 + (((ge * L + l) * K + kb) * 32 + r) * 8) + h;
+      return reinterpret_cast<const uint4 *>(sm8 + sm8_word(ge * L + l, K, kb, r, 0)) + h;
     };
     uint64_t *fk = sd.f_k[side];
     const int row = kb > 0 ? sd.row0[side] + kb - 1 : sd.row_p0[side];
@@ -525,6 +517,8 @@ __global__ void k_expand_sm8(const uint32_t *sm8, size_t N, int K, uint64_t *fck
        t += (size_t)gridDim.x * blockDim.x) {
     const int j = (int)(t % D4), kb = (int)(t / ((size_t)N * D4));
     const size_t e = (t / D4) % N;
+    // by[sm8_byte_of(e, K, kb, a)] and sm8_digit(byte, b) of digitpack.hpp, spelled out: through the
+    // helpers this kernel timed outside the pre-refactor form's spread
     const int a = j & (Q4 - 1), b = j >> 10, r = a & 31, k = a >> 5;
     const uint32_t byte = by[((e * K + kb) * 32 + r) * 32 + k];
     const uint32_t bit = (byte >> b) & 1u, neg = (byte >> (4 + b)) & 1u;
@@ -534,8 +528,8 @@ __global__ void k_expand_sm8(const uint32_t *sm8, size_t N, int K, uint64_t *fck
 hipError_t expand_sm8(const uint32_t *sm8, size_t N, int K, uint64_t *fck, hipStream_t st) {
   if (!N) return hipSuccess;
   if (K < 1 || K > 15) return hipErrorInvalidValue;
-  const size_t n = (size_t)K * N * D4, nb = (n + 255) / 256;
-  hipLaunchKernelGGL(k_expand_sm8, dim3((unsigned)(nb < 65536 ? nb : 65536)), dim3(256), 0, st, sm8, N, K, fck);
+  const size_t n = (size_t)K * N * D4;
+  hipLaunchKernelGGL(k_expand_sm8, dim3(grid_cap(blocks(n, 256))), dim3(256), 0, st, sm8, N, K, fck);
   return hipGetLastError();
 }
 
@@ -767,12 +761,12 @@ hipError_t decompose_n4k(const FusedSides &sd, size_t N, int lb, int L, int K, u
     for (int s = 0; s < sd.nside; s++) {
       if (sd.row0[s] < 0 || sd.row0[s] + K - 1 > 32 || sd.row_p0[s] > 32) return hipErrorInvalidValue;
       // the packed bytes (N K 256 words per side): the caller's planes, else the scratch
-      if (!s8.smg[s]) s8.smg[s] = reinterpret_cast<uint32_t *>(sm4) + (size_t)s * N * K * 256;
+      if (!s8.smg[s]) s8.smg[s] = reinterpret_cast<uint32_t *>(sm4) + (size_t)s * N * sm8_words(K);
       refold |= sd.f_k[s] != nullptr;
     }
     if (ncu < 32) return hipErrorInvalidValue;
-    const size_t threads = sd.nside * N * 256;
-    hipLaunchKernelGGL(k_pack_sm8, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, s8, N, K, err);
+    const size_t threads = sd.nside * N * SM8_PLANE_WORDS;  // one per word of a plane
+    hipLaunchKernelGGL(k_pack_sm8, dim3(blocks(threads, 256)), dim3(256), 0, st, s8, N, K, err);
     // 32 blocks per group of 8 units (8 XCDs x 4 quarters), one block per CU
     const unsigned grid = (unsigned)(ncu / 32 * 32);
     // outputs: f_coeff_k, f_k, the operand rows (each K N d words per side) and w_ccs_k
@@ -801,8 +795,8 @@ hipError_t decompose_n4k(const FusedSides &sd, size_t N, int lb, int L, int K, u
     }
     return hipGetLastError();
   }
-  const size_t words = sd.nside * N * Q4;
-  hipLaunchKernelGGL(k_pack_sm4, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, sd, N, K, sm4, err);
+  const size_t words = sd.nside * N * SM4_WORDS;
+  hipLaunchKernelGGL(k_pack_sm4, dim3(blocks(words, 256)), dim3(256), 0, st, sd, N, K, sm4, err);
   const size_t npair = (sd.nside * (N / L) * K + 1) / 2;
   // one block per CU, each taking the same number of work-item pairs
   const size_t per = (npair + 2 * ncu - 1) / (2 * ncu);

@@ -15,6 +15,7 @@
 // reference does not vendor (restated; parity unpinned).
 #include "gl.hpp"
 #include "kernels.hpp"
+#include "launch.hpp"
 #include "p2_consts.inc"
 
 namespace lfk {
@@ -260,8 +261,6 @@ __global__ void __launch_bounds__(256) k_merkle_verify(const Word *rows, size_t 
   if (live && i == 0) ok[e] = same && idx < nrows;
 }
 
-unsigned nb(size_t n) { return (unsigned)((n + 255) / 256); }
-
 }  // namespace
 
 int merkle_depth(size_t nrows) {
@@ -277,7 +276,7 @@ hipError_t merkle_verify(const Word *rows, size_t ntask, size_t span, size_t wid
                          uint8_t *ok, hipStream_t st) {
   if (!ntask) return hipSuccess;
   if (!nrows || !width || ntask > 2 * span || ntask > ((size_t)1 << 28)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_merkle_verify<Word>, dim3(nb(8 * ntask)), dim3(256), 0, st, rows, ntask, span, width, nrows,
+  hipLaunchKernelGGL(k_merkle_verify<Word>, dim3(blocks(8 * ntask, 256)), dim3(256), 0, st, rows, ntask, span, width, nrows,
                      merkle_depth(nrows), index, paths, roots, one_root ? (size_t)0 : (size_t)4, ok);
   return hipGetLastError();
 }
@@ -288,7 +287,7 @@ template hipError_t merkle_verify<uint32_t>(const uint32_t *, size_t, size_t, si
 
 hipError_t p2w8_permute(uint64_t *states, size_t n, hipStream_t st) {
   if (!n) return hipSuccess;
-  hipLaunchKernelGGL(k_p2w8_permute, dim3(nb(n)), dim3(256), 0, st, states, n);
+  hipLaunchKernelGGL(k_p2w8_permute, dim3(blocks(n, 256)), dim3(256), 0, st, states, n);
   return hipGetLastError();
 }
 
@@ -309,13 +308,13 @@ size_t merkle_nodes(size_t nrows) {
 
 hipError_t merkle_tree(const uint64_t *rows, size_t nrows, size_t width, uint64_t *nodes, hipStream_t st) {
   if (!nrows || !width) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_merkle_leaves, dim3(nb(8 * nrows)), dim3(256), 0, st, rows, nrows, width, nodes);
+  hipLaunchKernelGGL(k_merkle_leaves, dim3(blocks(8 * nrows, 256)), dim3(256), 0, st, rows, nrows, width, nodes);
   size_t off = 0, n = nrows <= 1 ? 1 : nrows + nrows % 2;
   hipError_t e;
   if (n > nrows && (e = hipMemsetAsync(nodes + 4 * nrows, 0, 32 * (n - nrows), st)) != hipSuccess) return e;
   while (n > 1) {
     const size_t nn = n == 2 ? 1 : ((n / 2 + 1) & ~(size_t)1);
-    hipLaunchKernelGGL(k_merkle_level, dim3(nb(8 * (n / 2))), dim3(256), 0, st, nodes + 4 * off, n / 2,
+    hipLaunchKernelGGL(k_merkle_level, dim3(blocks(8 * (n / 2), 256)), dim3(256), 0, st, nodes + 4 * off, n / 2,
                        nodes + 4 * (off + n));
     if (nn > n / 2 && (e = hipMemsetAsync(nodes + 4 * (off + n + n / 2), 0, 32 * (nn - n / 2), st)) != hipSuccess)
       return e;
@@ -345,11 +344,11 @@ hipError_t memtree_apply(uint64_t *nodes, size_t npages, size_t width, const Mem
   LayerOffsets lo;
   const int depth = merkle_layer_offsets(npages, lo.off, MEMTREE_MAX_DEPTH + 1);
   if (!npages || !width || depth < 0) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_memtree_leaves, dim3(nb(8 * k)), dim3(256), 0, st, b.pages, k, width, b.ver);
+  hipLaunchKernelGGL(k_memtree_leaves, dim3(blocks(8 * k, 256)), dim3(256), 0, st, b.pages, k, width, b.ver);
   for (int l = 0; l < depth; l++)
-    hipLaunchKernelGGL(k_memtree_layer, dim3(nb(8 * k)), dim3(256), 0, st, nodes + 4 * lo.off[l], b.pg, b.prev, k, l,
+    hipLaunchKernelGGL(k_memtree_layer, dim3(blocks(8 * k, 256)), dim3(256), 0, st, nodes + 4 * lo.off[l], b.pg, b.prev, k, l,
                        depth, b.ver + (size_t)l * k * 4, b.ver + (size_t)(l + 1) * k * 4, b.paths);
-  hipLaunchKernelGGL(k_memtree_writeback, dim3(nb(4 * k * (depth + 1))), dim3(256), 0, st, nodes, lo, b.pg, b.last, k,
+  hipLaunchKernelGGL(k_memtree_writeback, dim3(blocks(4 * k * (depth + 1), 256)), dim3(256), 0, st, nodes, lo, b.pg, b.last, k,
                      depth, b.ver);
   return hipGetLastError();
 }
@@ -358,7 +357,7 @@ hipError_t memtree_apply(uint64_t *nodes, size_t npages, size_t width, const Mem
 hipError_t hash_w8_rows(const uint64_t *rows, size_t nrows, size_t width, uint64_t *out, hipStream_t st) {
   if (!nrows) return hipSuccess;
   if (!width) return hipMemsetAsync(out, 0, 32 * nrows, st);  // the empty input's digest is the zero state
-  hipLaunchKernelGGL(k_merkle_leaves, dim3(nb(8 * nrows)), dim3(256), 0, st, rows, nrows, width, out);
+  hipLaunchKernelGGL(k_merkle_leaves, dim3(blocks(8 * nrows, 256)), dim3(256), 0, st, rows, nrows, width, out);
   return hipGetLastError();
 }
 

@@ -16,6 +16,7 @@
 // without materialising the t x nz MLEs of 2^s ring elements each.
 #include "frag.hpp"
 #include "kernels.hpp"
+#include "launch.hpp"
 #include "slot.hpp"
 
 namespace lfk {
@@ -377,8 +378,6 @@ int dots_nsplit(const CcsDev &M, int nz) {
   return k < 1 ? 1 : k;
 }
 
-unsigned nblk(size_t n, int t) { return (unsigned)((n + t - 1) / t); }
-
 // Mz MLE outputs above this many bytes are written with streaming stores: the zkvm's
 // 3.1 GB otherwise cycle through L2 and evict the z rows the gathers re-read (k_csr
 // 1.43 -> 1.32 ms; the transposes' 474 MB of weights gain nothing and keep plain stores)
@@ -400,7 +399,7 @@ hipError_t csr(const CcsDev &M, const uint64_t *rp, size_t rp_stride, int na, co
                bool nt = false, const uint64_t *rv = nullptr) {
   if (!nrows || !ntask) return hipSuccess;
   const int d = M.d, tb = slot_words(d), ns = d / tb, spb = ns < MT ? ns : MT;
-  const dim3 grid(nblk(nrows, MT / spb), (unsigned)ntask, (unsigned)(ns / spb));
+  const dim3 grid(blocks(nrows, MT / spb), (unsigned)ntask, (unsigned)(ns / spb));
   // the entries' values in this product's own order when there is a copy (sv: scalar,
   // rv: ring-valued), else gathered through vidx
   const uint64_t *val = M.sval ? sv : (rv ? rv : M.val);
@@ -448,23 +447,23 @@ hipError_t zcomb(const CcsDev &M, const uint64_t *z, const uint64_t *zeta, int n
     const int kcn = (3 * nz + 63) / 64, nrt = (M.t + ZC_J - 1) / ZC_J;
     const size_t nct = (M.n + 15) / 16;
     v4i *af = reinterpret_cast<v4i *>(scr + (size_t)M.t * nz * M.d), *bf = af + (size_t)ns * nrt * kcn * 512;
-    hipLaunchKernelGGL(k_zeta_pows<3>, dim3(nblk((size_t)M.t * nz * ns, 256)), dim3(256), 0, st, zeta, nz, M.t, M.d, pw);
+    hipLaunchKernelGGL(k_zeta_pows<3>, dim3(blocks((size_t)M.t * nz * ns, 256)), dim3(256), 0, st, zeta, nz, M.t, M.d, pw);
     if (kcn > ZC_KCN_MAX) {  // more chunks than the i32 accumulators hold: the scalar form, pw | (unused) | y
-      hipLaunchKernelGGL(k_zcomb<3>, dim3(nblk((size_t)M.t * M.n * ns, 256)), dim3(256), 0, st, pw, z, nz, M.t, M.n,
+      hipLaunchKernelGGL(k_zcomb<3>, dim3(blocks((size_t)M.t * M.n * ns, 256)), dim3(256), 0, st, pw, z, nz, M.t, M.n,
                          M.d, y);
       return hipGetLastError();
     }
-    hipLaunchKernelGGL(k_zc_afrag, dim3(nblk((size_t)ns * nrt * kcn * 64, 256)), dim3(256), 0, st, pw, nz, M.t, nrt,
+    hipLaunchKernelGGL(k_zc_afrag, dim3(blocks((size_t)ns * nrt * kcn * 64, 256)), dim3(256), 0, st, pw, nz, M.t, nrt,
                        kcn, af);
-    hipLaunchKernelGGL(k_zc_bfrag, dim3(nblk(nct * ns * kcn * 64, 512)), dim3(512), 0, st, z, nz, M.n, kcn, nct, bf);
+    hipLaunchKernelGGL(k_zc_bfrag, dim3(blocks(nct * ns * kcn * 64, 512)), dim3(512), 0, st, z, nz, M.n, kcn, nct, bf);
     const dim3 grid((unsigned)(8 * ((nct + 7) / 8) * ((nrt + ZC_WAVES - 1) / ZC_WAVES)));
     if (3 * nz < 64)
       hipLaunchKernelGGL(k_zcomb_mfma<true>, grid, dim3(64 * ZC_WAVES), 0, st, af, bf, M.t, M.n, nrt, kcn, nct, y);
     else
       hipLaunchKernelGGL(k_zcomb_mfma<false>, grid, dim3(64 * ZC_WAVES), 0, st, af, bf, M.t, M.n, nrt, kcn, nct, y);
   } else {
-    hipLaunchKernelGGL(k_zeta_pows<1>, dim3(nblk((size_t)M.t * nz * ns, 256)), dim3(256), 0, st, zeta, nz, M.t, M.d, pw);
-    hipLaunchKernelGGL(k_zcomb<1>, dim3(nblk((size_t)M.t * M.n * ns, 256)), dim3(256), 0, st, pw, z, nz, M.t, M.n,
+    hipLaunchKernelGGL(k_zeta_pows<1>, dim3(blocks((size_t)M.t * nz * ns, 256)), dim3(256), 0, st, zeta, nz, M.t, M.d, pw);
+    hipLaunchKernelGGL(k_zcomb<1>, dim3(blocks((size_t)M.t * M.n * ns, 256)), dim3(256), 0, st, pw, z, nz, M.t, M.n,
                        M.d, y);
   }
   return hipGetLastError();
@@ -481,7 +480,7 @@ __global__ void k_gather_entries(const uint64_t *val, const uint32_t *idx, size_
 
 hipError_t gather_entries(const uint64_t *val, const uint32_t *idx, size_t nnz, int d, uint64_t *out, hipStream_t st) {
   if (!nnz) return hipSuccess;
-  hipLaunchKernelGGL(k_gather_entries, dim3(nblk(nnz * d, 256)), dim3(256), 0, st, val, idx, nnz, d, out);
+  hipLaunchKernelGGL(k_gather_entries, dim3(blocks(nnz * d, 256)), dim3(256), 0, st, val, idx, nnz, d, out);
   return hipGetLastError();
 }
 
@@ -501,7 +500,7 @@ hipError_t mz_mles(const CcsDev &M, const uint64_t *z, int nz, int nv, uint64_t 
   if (na < 1) return hipSuccess;
   if (M.m < ((size_t)1 << nv)) {  // the MLEs' zero padding: rows m .. 2^nv - 1 of each
     const size_t tail = len - M.m * M.d, total = (size_t)nz * na * tail;
-    hipLaunchKernelGGL(k_zero_tails, dim3(nblk(total, 256)), dim3(256), 0, st, out, len, M.m * M.d, tail, total);
+    hipLaunchKernelGGL(k_zero_tails, dim3(blocks(total, 256)), dim3(256), 0, st, out, len, M.m * M.d, tail, total);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
@@ -542,7 +541,7 @@ hipError_t mz_challenged_pair(const CcsDev &M, const uint64_t *z0, const uint64_
   }
   if (!M.m) return hipSuccess;
   const int spb = ns < MT ? ns : MT;
-  const dim3 grid(nblk(M.m, MT / spb), 1, (unsigned)(ns / spb));
+  const dim3 grid(blocks(M.m, MT / spb), 1, (unsigned)(ns / spb));
   const uint64_t *val = M.sval ? M.svh : (M.vh ? M.vh : M.val);
   const uint32_t *vidx = M.sval || M.vh ? nullptr : M.hidx;
 #define LF_CSRP(TB, SC)                                                                                       \
@@ -598,7 +597,7 @@ hipError_t mz_dots(const CcsDev &M, const uint64_t *w, const uint64_t *z, int nz
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || nsplit == 1) return e;
   const size_t len = (size_t)nz * M.t * M.d;
-  hipLaunchKernelGGL(k_dots_sum, dim3(nblk(len, 256)), dim3(256), 0, st, partial, nsplit, len, out);
+  hipLaunchKernelGGL(k_dots_sum, dim3(blocks(len, 256)), dim3(256), 0, st, partial, nsplit, len, out);
   return hipGetLastError();
 }
 

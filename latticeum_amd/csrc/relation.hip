@@ -10,6 +10,7 @@
 // -- with the Hadamard products and the c-weighted sum taken on the row sums in
 // registers: no M_j z vector is written, and the answer is one word per z.
 #include "kernels.hpp"
+#include "launch.hpp"
 #include "slot.hpp"
 
 namespace lfk {
@@ -177,10 +178,9 @@ __global__ void __launch_bounds__(RT) k_first_diff(const uint64_t *a, const uint
   if (threadIdx.x == 0 && bad != NONE) atomicMin(out, (unsigned long long)bad);
 }
 
-unsigned nblk(size_t n, int t) { return (unsigned)((n + t - 1) / t); }
 // blocks of a grid-stride pass over n items: one item per thread up to a few waves per CU
 unsigned stride_blocks(size_t n) {
-  const size_t b = (n + RT - 1) / RT;
+  const size_t b = blocks(n, RT);
   return (unsigned)(b < 1 ? 1 : b > 4096 ? 4096 : b);
 }
 
@@ -192,7 +192,7 @@ hipError_t ccs_relation(const CcsDev &M, const uint64_t *z, int nz, const uint64
   hipError_t e = hipMemsetAsync(first_bad, 0xFF, (size_t)nz * 8, st);
   if (e != hipSuccess || !M.m) return e;
   const int d = M.d, tb = slot_words(d), ns = d / tb, spb = ns < RT ? ns : RT;
-  const dim3 grid(nblk(M.m, RT / spb), (unsigned)nz, (unsigned)(ns / spb));
+  const dim3 grid(blocks(M.m, RT / spb), (unsigned)nz, (unsigned)(ns / spb));
   unsigned long long *fb = reinterpret_cast<unsigned long long *>(first_bad);
 #define LF_REL(TB, SC, VAL)                                                                                          \
   hipLaunchKernelGGL((k_ccs_relation<TB, SC>), grid, dim3(RT), 0, st, M.rp, M.m + 1, M.col, VAL, M.m, d, z, M.n * d, \

@@ -364,7 +364,7 @@ int replay(const lf_ccs_desc *ccs, const lf_params *pr, const lf_lcccs *acc, con
 
 // RotSum of the short challenges (coefficient form) with the flattened theta_i:
 // v0[j][c] = sum_i sum_r theta_i[r][c] coeff_j(X^r rho_i) (rotation.rs:84-101), Phi_72
-// (X^24 = X^12 - 1, X^36 = -1); the host twin of kernels.hip k_rot_lin
+// (X^24 = X^12 - 1, X^36 = -1); the host twin of fold.hip k_rot_lin
 uint64_t rot_coeff(const uint64_t *a, int j, int r) {
   uint64_t v = j >= r ? a[j - r] : 0;
   if (j >= 12 && r > j - 12) v = gl::add(v, a[j + 12 - r]);

@@ -283,5 +283,26 @@ __device__ __forceinline__ uint64_t *stockham4(uint64_t *x, uint64_t *y, const u
   }
   return x;
 }
+// the kernels that run stockham4 on one element per workgroup use this many threads
+template <int D>
+struct NT {
+  static constexpr int T = D / 4 < 256 ? D / 4 : 256;  // threads per element
+};
+
+// a Phi_72 element (24 u64, 192 B) as 12 16-B vector loads / stores
+__device__ __forceinline__ void ld24(const uint64_t *p, uint64_t *c) {
+  const ulonglong2 *src = reinterpret_cast<const ulonglong2 *>(p);
+#pragma unroll
+  for (int i = 0; i < 12; i++) {
+    ulonglong2 v = src[i];
+    c[2 * i] = v.x;
+    c[2 * i + 1] = v.y;
+  }
+}
+__device__ __forceinline__ void st24(uint64_t *p, const uint64_t *c) {
+  ulonglong2 *dst = reinterpret_cast<ulonglong2 *>(p);
+#pragma unroll
+  for (int i = 0; i < 12; i++) dst[i] = make_ulonglong2(c[2 * i], c[2 * i + 1]);
+}
 
 }  // namespace ring

@@ -15,6 +15,7 @@
 // slot is an Fq3 (Phi_72, TB = 3 words) or an Fq (X^d + 1, TB = 1).
 #include "gl.hpp"
 #include "kernels.hpp"
+#include "launch.hpp"
 #include "ring.hpp"
 #include "slot.hpp"
 
@@ -811,12 +812,10 @@ __global__ void __launch_bounds__(256) k_mle_lincomb(const uint64_t *mles, size_
   s_store(o, s_add(s_load<TB>(o), sacc_final(la)));
 }
 
-unsigned blocks_of(size_t n, int t) { return (unsigned)((n + t - 1) / t); }
-
 template <int TB>
 hipError_t dispatch_eq(const uint64_t *r, int nv, int d, uint64_t *out, hipStream_t st) {
   const size_t n = ((size_t)(d / TB)) << nv;
-  hipLaunchKernelGGL(k_eq_table<TB>, dim3(blocks_of(n, 256)), dim3(256), 0, st, r, nv, d, out);
+  hipLaunchKernelGGL(k_eq_table<TB>, dim3(blocks(n, 256)), dim3(256), 0, st, r, nv, d, out);
   return hipGetLastError();
 }
 
@@ -837,12 +836,12 @@ hipError_t mle_fix_first(const uint64_t *in, size_t in_stride, int nm, size_t ha
   if (tb == 3) {
     Sv<3> r;
     for (int i = 0; i < 3; i++) r.c[i] = r_base[i];
-    hipLaunchKernelGGL(k_fix_first<3>, dim3(blocks_of(n, 256)), dim3(256), 0, st, in, in_stride, ptrs, nm, half, d, r,
+    hipLaunchKernelGGL(k_fix_first<3>, dim3(blocks(n, 256)), dim3(256), 0, st, in, in_stride, ptrs, nm, half, d, r,
                        out, out_stride);
   } else {
     Sv<1> r;
     r.c[0] = r_base[0];
-    hipLaunchKernelGGL(k_fix_first<1>, dim3(blocks_of(n, 256)), dim3(256), 0, st, in, in_stride, ptrs, nm, half, d, r,
+    hipLaunchKernelGGL(k_fix_first<1>, dim3(blocks(n, 256)), dim3(256), 0, st, in, in_stride, ptrs, nm, half, d, r,
                        out, out_stride);
   }
   return hipGetLastError();
@@ -881,9 +880,9 @@ size_t round_partial_elems(int d, size_t half, int nevals, int nf) {
 hipError_t fold_weights(const uint64_t *mu, int nk, int tau, int d, uint64_t *w, hipStream_t st) {
   const int tb = slot_words(d), n = nk * (d / tb);
   if (tb == 3)
-    hipLaunchKernelGGL(k_fold_weights<3>, dim3(blocks_of(n, 256)), dim3(256), 0, st, mu, nk, tau, d, w);
+    hipLaunchKernelGGL(k_fold_weights<3>, dim3(blocks(n, 256)), dim3(256), 0, st, mu, nk, tau, d, w);
   else
-    hipLaunchKernelGGL(k_fold_weights<1>, dim3(blocks_of(n, 256)), dim3(256), 0, st, mu, nk, tau, d, w);
+    hipLaunchKernelGGL(k_fold_weights<1>, dim3(blocks(n, 256)), dim3(256), 0, st, mu, nk, tau, d, w);
   return hipGetLastError();
 }
 
@@ -947,12 +946,12 @@ hipError_t fix_fhat_digits(const uint64_t *fc0, const uint64_t *fc1, int K, size
   if (tb == 3) {
     Sv<3> r;
     for (int i = 0; i < 3; i++) r.c[i] = r_base[i];
-    hipLaunchKernelGGL(k_fix_fhat_digits<3>, dim3(blocks_of(n, 256)), dim3(256), 0, st, fc0, fc1, K, N, wstride, nf,
+    hipLaunchKernelGGL(k_fix_fhat_digits<3>, dim3(blocks(n, 256)), dim3(256), 0, st, fc0, fc1, K, N, wstride, nf,
                        half, d, r, out, out_stride);
   } else {
     Sv<1> r;
     r.c[0] = r_base[0];
-    hipLaunchKernelGGL(k_fix_fhat_digits<1>, dim3(blocks_of(n, 256)), dim3(256), 0, st, fc0, fc1, K, N, wstride, nf,
+    hipLaunchKernelGGL(k_fix_fhat_digits<1>, dim3(blocks(n, 256)), dim3(256), 0, st, fc0, fc1, K, N, wstride, nf,
                        half, d, r, out, out_stride);
   }
   return hipGetLastError();
@@ -962,10 +961,10 @@ hipError_t fhat_lincomb_digits(const uint64_t *fc, int nw, size_t N, size_t wstr
                                int d, uint64_t *io, hipStream_t st) {
   const size_t npts = (size_t)1 << nv, n = npts * (size_t)(d / slot_words(d));
   if (slot_words(d) == 3)
-    hipLaunchKernelGGL(k_fhat_lincomb_digits<3>, dim3(blocks_of(n, 256)), dim3(256), 0, st, fc, nw, N, wstride, coef,
+    hipLaunchKernelGGL(k_fhat_lincomb_digits<3>, dim3(blocks(n, 256)), dim3(256), 0, st, fc, nw, N, wstride, coef,
                        npts, d, io);
   else
-    hipLaunchKernelGGL(k_fhat_lincomb_digits<1>, dim3(blocks_of(n, 256)), dim3(256), 0, st, fc, nw, N, wstride, coef,
+    hipLaunchKernelGGL(k_fhat_lincomb_digits<1>, dim3(blocks(n, 256)), dim3(256), 0, st, fc, nw, N, wstride, coef,
                        npts, d, io);
   return hipGetLastError();
 }
@@ -1101,7 +1100,7 @@ size_t round_lin_sparse_ppb(int d) {
 hipError_t pair_sum(const uint64_t *E, size_t half, int d, uint64_t *out, hipStream_t st) {
   const size_t n = half * d;
   if (!n) return hipSuccess;
-  hipLaunchKernelGGL(k_pair_sum, dim3(blocks_of(n, 256)), dim3(256), 0, st, E, half, d, out);
+  hipLaunchKernelGGL(k_pair_sum, dim3(blocks(n, 256)), dim3(256), 0, st, E, half, d, out);
   return hipGetLastError();
 }
 
@@ -1151,9 +1150,9 @@ hipError_t mle_lincomb(const uint64_t *mles, size_t stride, int nm, const uint64
   const int tb = slot_words(d);
   const size_t nt = n * (size_t)(d / tb);
   if (tb == 3)
-    hipLaunchKernelGGL(k_mle_lincomb<3>, dim3(blocks_of(nt, 256)), dim3(256), 0, st, mles, stride, nm, coef, n, d, io);
+    hipLaunchKernelGGL(k_mle_lincomb<3>, dim3(blocks(nt, 256)), dim3(256), 0, st, mles, stride, nm, coef, n, d, io);
   else
-    hipLaunchKernelGGL(k_mle_lincomb<1>, dim3(blocks_of(nt, 256)), dim3(256), 0, st, mles, stride, nm, coef, n, d, io);
+    hipLaunchKernelGGL(k_mle_lincomb<1>, dim3(blocks(nt, 256)), dim3(256), 0, st, mles, stride, nm, coef, n, d, io);
   return hipGetLastError();
 }
 
@@ -1197,7 +1196,7 @@ hipError_t get_fhat(const uint64_t *f_coeff, size_t N, int d, int nv, uint64_t *
   if (N > npts || nw < 1) return hipErrorInvalidValue;
   const size_t per = (size_t)(d == 24 ? 3 : 1) * npts * d, total = per * nw;
   if (!total) return hipSuccess;
-  hipLaunchKernelGGL(k_get_fhat, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, f_coeff, N, wstride, d, npts,
+  hipLaunchKernelGGL(k_get_fhat, dim3(blocks(total, 256)), dim3(256), 0, st, f_coeff, N, wstride, d, npts,
                      per, total, out);
   return hipGetLastError();
 }
@@ -1206,7 +1205,7 @@ hipError_t assemble_z(const uint64_t *x, const uint64_t *w, int nz, size_t l1, s
                       hipStream_t st) {
   const size_t total = (size_t)nz * (l1 + W) * d;
   if (!total) return hipSuccess;
-  hipLaunchKernelGGL(k_assemble_z, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x, w, l1, W, d, total, out);
+  hipLaunchKernelGGL(k_assemble_z, dim3(blocks(total, 256)), dim3(256), 0, st, x, w, l1, W, d, total, out);
   return hipGetLastError();
 }
 

@@ -18,6 +18,7 @@ import pytest
 
 import latticeum_amd as LA
 import oracle as O
+from planes_decode import decode_planes, planes_u64
 from test_gpu_parity import make_rho, oracle_fold_hot, params, rand, valid_f_coeff
 
 pytestmark = pytest.mark.gpu
@@ -106,10 +107,6 @@ def reference(d, W, wkind, short=True, seed=0):
     return ref
 
 
-def planes_u64(d, K, N):
-    return K * N if d == 24 else N * 256 if d == 1024 else N * K * 128
-
-
 def make_bufs(torch, ref, d, W, packed):
     pr = params(d)
     K, N = pr.K, W * pr.L
@@ -183,6 +180,31 @@ def run_step(c, d, W, wkind="rand", packed=True, short=True):
                                         (4096, 16, True), (4096, 17, True), (1024, 17, False)])
 def test_step_shapes(ctx, d, W, packed):
     run_step(ctx, d, W, packed=packed)
+
+
+# the smallest shapes at which each layout can go wrong. d = 24, W = 17: one full 16-group
+# unit of the wave-local decomposition plus a ragged one; d = 1024, W = 3: odd, so the
+# half-wave pairing rounds up; d = 4096: the smallest W of the step tests above
+@pytest.mark.parametrize("d,W", [(24, 17), (1024, 3), (4096, 16)])
+def test_packed_planes_layout(ctx, d, W):
+    """planes[0..1] of a packed step, downloaded and decoded by tests/planes_decode.py (written
+    from include/lf.h's wording), are the oracle's decompose_witness digits -- compared
+    directly, not through lf_dev_expand_planes, so a writer and a reader that moved together
+    would not pass"""
+    import torch
+    pr = params(d)
+    K, N = pr.K, W * pr.L
+    ref = reference(d, W, "rand")
+    sch = make_scheme(torch, ctx, ref, d, W)
+    keep, b = make_bufs(torch, ref, d, W, True)
+    torch.cuda.synchronize()
+    ctx.dev_fold_step(sch, pr, W, b)
+    ctx.sync()
+    for s in range(2):
+        got = decode_planes(keep["planes"][s].cpu().numpy(), d, K, N)
+        want = signed(ref["sides"][s][0]).reshape(K, N, d)
+        assert np.abs(want).max() == 1 and np.abs(want).any(axis=(1, 2))[:4].all()
+        assert np.array_equal(got, want), f"side {s}"
 
 
 def test_plane0_dead_everywhere(ctx):

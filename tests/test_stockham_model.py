@@ -17,7 +17,7 @@ SIZES = [16, 32, 64, 128, 512, 1024, 2048]
 
 
 def nt(D):
-    """kernels.hip NT<D>::T: threads per element"""
+    """ring.hpp NT<D>::T: threads per element"""
     return min(D // 4, 256)
 
 

@@ -393,6 +393,16 @@ int lf_dev_poseidon2_permute_rounds(lf_ctx *ctx, uint64_t *states, size_t n, int
  * LF_ERR_INVALID_ARG (+ lf_ctx_last_error) for an unknown op or an s or m outside its range. */
 int lf_dev_gl_probe(lf_ctx *ctx, int op, const uint64_t *a, const uint64_t *b, int s, int m, uint64_t *out,
                     size_t n);
+/* test aid: whether the context's last fold step (lf_dev_fold_step and its batch, partial /
+ * finish and lf_dev_fold_combine forms, lf_fold_hot) judged rho short. The coefficient-form
+ * folds (d = 1024 after the fused decomposition: every coefficient of every rho_i in
+ * [-127, 127]; d = 24 with b_small = 2: in [-32, 32]) decide it on the device, per step, with
+ * no host synchronisation; this call waits for the context's stream and reads that flag:
+ * *out = 0 rho was short and f_0 was folded in coefficient form, 1 it was not and the
+ * NTT-form fold ran instead, -1 the step took a path that has no such flag. It launches
+ * nothing and leaves the decomposition-overflow state to lf_ctx_sync. In a batch every step's
+ * context reports its own step. */
+int lf_ctx_fold_flag(lf_ctx *ctx, int *out);
 /* synthetic inputs: element i = SplitMix64(seed, i) re-mixed until < p */
 int lf_dev_fill_uniform(lf_ctx *ctx, uint64_t *out, size_t n, uint64_t seed);
 /* out[c] = sum_r in[r][c] mod p  (reduce of all-gathered accumulators) */

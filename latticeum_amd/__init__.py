@@ -93,6 +93,14 @@ class Context:
     def sync(self):
         self.check(self.lib.lf_ctx_sync(self.h))
 
+    def fold_flag(self) -> int:
+        """test aid (lf_ctx_fold_flag): waits for the stream; 1 if the last fold step judged rho
+        not short (the NTT-form fold ran), 0 if short (the coefficient-form fold), -1 if the
+        step's path has no such flag"""
+        out = C.c_int()
+        self.check(self.lib.lf_ctx_fold_flag(self.h, C.byref(out)))
+        return out.value
+
     def use_cu_mask(self, cus):
         """run this context's work on a stream of its own restricted to the
         compute units `cus` (iterable of CU indices); lf_stream_create_cu_mask"""

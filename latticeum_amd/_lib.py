@@ -138,6 +138,7 @@ SIGNATURES = {
     "lf_dev_poseidon2_permute": (I, [VP, VP, SZ]),
     "lf_dev_poseidon2_permute_rounds": (I, [VP, VP, SZ, I]),
     "lf_dev_gl_probe": (I, [VP, I, VP, VP, I, I, VP, SZ]),
+    "lf_ctx_fold_flag": (I, [VP, C.POINTER(I)]),
     "lf_dev_fill_uniform": (I, [VP, VP, SZ, U64]),
     "lf_dev_modp_sum": (I, [VP, VP, I, SZ, VP]),
     "lf_dev_limb_split": (I, [VP, VP, SZ, VP, VP]),

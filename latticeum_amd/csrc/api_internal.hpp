@@ -69,6 +69,7 @@ struct lf_ctx {
   int32_t *fpart = nullptr;     // coefficient-form fold with few elements: per witness-split partial sums
   size_t fpart_elems = 0;
   size_t faux_elems = 0;
+  long fold_flag_at = -1;       // the last fold_finish's not-short flag: its u64 index in faux, -1 = a path without one
   uint64_t *sink = nullptr;     // 32 KiB row the fused decompositions store work past the end into
   uint8_t *dead = nullptr;      // dead-unit flags of the operand rows (lfk::DeadUnits) [2 nch][32]
   size_t dead_elems = 0;

@@ -336,6 +336,7 @@ int fold_finish(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, int lb, int 
   // cm1_out: y_1[0] is in place too and cm_i is made from side 1's planes
   LF_HIP(c, lfk::y0_cm0(b->acc_cm, cm_i, b->y[0], b->y[1], b->rho, kappa, d, lbs, K, b->cm0, c->cur, cm1_out));
   const StepState &st = c->step;
+  c->fold_flag_at = -1;  // lf_ctx_fold_flag: set below where the path has a flag
   // the f_k rows of both sides, for the NTT-form fold
   auto fk_rows = [&] {
     lfk::VecPtrs fx{};
@@ -359,6 +360,7 @@ int fold_finish(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, int lb, int 
       uint64_t *rc = c->faux;
       uint8_t *tab = reinterpret_cast<uint8_t *>(c->faux + (size_t)nw * 1024);
       int *bad = reinterpret_cast<int *>(c->faux + aux - 1);
+      c->fold_flag_at = (long)(aux - 1);
       {
         PhaseTimer pt(c, LF_PHASE_FOLD);
         for (int s = 0; s < 2; s++)
@@ -390,6 +392,7 @@ int fold_finish(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, int lb, int 
       LF_TRY(grow(c, c->faux, c->faux_elems, (size_t)nw * 13 + 1));
       uint32_t *rc = reinterpret_cast<uint32_t *>(c->faux);  // 25 packed words per witness
       int *bad = reinterpret_cast<int *>(c->faux + (size_t)nw * 13);
+      c->fold_flag_at = (long)nw * 13;
       {
         PhaseTimer pt(c, LF_PHASE_FOLD);
         LF_HIP(c, lfk::fold_phi72_rho(b->rho, nw, rc, bad, c->cur));

@@ -449,6 +449,20 @@ int lf_ctx_sync(lf_ctx *c) {
   return LF_OK;
 }
 
+// test aid: the not-short flag the last fold_finish left at the tail of faux (it only
+// waits and reads; the decomposition-overflow state stays for lf_ctx_sync)
+int lf_ctx_fold_flag(lf_ctx *c, int *out) {
+  DevGuard g(c);
+  if (!c || !out) return LF_ERR_INVALID_ARG;
+  LF_HIP(c, hipStreamSynchronize(c->cur));
+  *out = -1;
+  if (c->fold_flag_at < 0 || !c->faux || (size_t)c->fold_flag_at >= c->faux_elems) return LF_OK;
+  int bad = 0;
+  LF_HIP(c, hipMemcpy(&bad, c->faux + c->fold_flag_at, sizeof(int), hipMemcpyDeviceToHost));
+  *out = bad ? 1 : 0;
+  return LF_OK;
+}
+
 int lf_ctx_reserve(lf_ctx *c, size_t kappa, size_t ncols, int d, int nvec) {
   DevGuard g(c);
   if (!c || !ring_ok(d) || nvec < 1 || nvec > LF_MAX_VECS) return LF_ERR_INVALID_ARG;

@@ -107,18 +107,18 @@ def reference(d, W, wkind, short=True, seed=0):
     return ref
 
 
-def make_bufs(torch, ref, d, W, packed):
+def make_bufs(torch, ref, d, W, packed, kappa=KAPPA):
     pr = params(d)
     K, N = pr.K, W * pr.L
     dev = lambda x: torch.from_numpy(np.array(x, copy=True).view(np.int64)).cuda()
     z = lambda n: torch.zeros(n, dtype=torch.int64, device="cuda")
     keep = {
         "w_ccs": dev(ref["w_ccs"]), "acc_cm": dev(ref["acc_cm"]), "acc_f_coeff": dev(ref["acc_fc"]),
-        "rho": dev(ref["rho"]), "f_coeff": z(N * d), "f": z(N * d), "cm": z(KAPPA * d),
+        "rho": dev(ref["rho"]), "f_coeff": z(N * d), "f": z(N * d), "cm": z(kappa * d),
         "fk_coeff": [z(K * N * d) for _ in range(2)] if not packed else [None, None],
         "fk": [z(K * N * d) for _ in range(2)] if not packed else [None, None],
-        "wk": [z(K * W * d) for _ in range(2)], "y": [z(K * KAPPA * d) for _ in range(2)],
-        "f0": z(N * d), "f0_coeff": z(N * d), "w_ccs0": z(W * d), "cm0": z(KAPPA * d),
+        "wk": [z(K * W * d) for _ in range(2)], "y": [z(K * kappa * d) for _ in range(2)],
+        "f0": z(N * d), "f0_coeff": z(N * d), "w_ccs0": z(W * d), "cm0": z(kappa * d),
         "planes": [z(planes_u64(d, K, N)) for _ in range(2)] if packed else [None, None],
     }
     b = LA.LfFoldStepBufs()
@@ -131,12 +131,12 @@ def make_bufs(torch, ref, d, W, packed):
     return keep, b
 
 
-def make_scheme(torch, c, ref, d, W):
+def make_scheme(torch, c, ref, d, W, kappa=KAPPA):
     At = torch.from_numpy(np.array(ref["A"], copy=True).view(np.int64)).cuda()
-    return LA.AjtaiCommitmentScheme(c, device_tensor=At, kappa=KAPPA, ncols=W * params(d).L, d=d)
+    return LA.AjtaiCommitmentScheme(c, device_tensor=At, kappa=kappa, ncols=W * params(d).L, d=d)
 
 
-def check_outputs(torch, c, ref, keep, d, W, packed):
+def check_outputs(torch, c, ref, keep, d, W, packed, kappa=KAPPA):
     """every output buffer against the oracle's step"""
     pr = params(d)
     K, N = pr.K, W * pr.L
@@ -144,8 +144,8 @@ def check_outputs(torch, c, ref, keep, d, W, packed):
     want, sides = ref["want"], ref["sides"]
     for key in ("f_coeff", "f", "cm", "f0", "f0_coeff", "w_ccs0", "cm0"):
         assert np.array_equal(h(keep[key]), want[key]), key
-    y = np.concatenate([h(t) for t in keep["y"]]).reshape(2, K, KAPPA * d)
-    oy = want["y"].reshape(2, K, KAPPA * d)
+    y = np.concatenate([h(t) for t in keep["y"]]).reshape(2, K, kappa * d)
+    oy = want["y"].reshape(2, K, kappa * d)
     for s in range(2):
         for k in range(K):
             assert np.array_equal(y[s, k], oy[s, k]), f"y side {s} plane {k}"

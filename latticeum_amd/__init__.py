@@ -774,22 +774,41 @@ class Prover:
         return fold_replay(self.pr, self.t, self.ccs.m, self.l, self.degree, self.c, self.S, self.kappa, acc, cm_i,
                            x_ccs, proof, repr)
 
+    def _raise(self, rc: int):
+        raise LfError(rc, self.lib.lf_prover_last_error(self.h).decode() or self.lib.lf_status_string(rc).decode())
+
+    def _lcccs_out(self):
+        """an empty LCCCS dict and the LfLcccsMut over its arrays"""
+        from ._lib import LfLcccsMut
+        d = self.d
+        out = {"r": np.zeros(self.s * d, np.uint64), "v": np.zeros(self.tau * d, np.uint64),
+               "cm": np.zeros(self.kappa * d, np.uint64), "u": np.zeros(self.t * d, np.uint64),
+               "x_w": np.zeros(max(self.l, 1) * d, np.uint64), "h": np.zeros(d, np.uint64)}
+        return out, LfLcccsMut(*[out[k].ctypes.data for k in ("r", "v", "cm", "u", "x_w", "h")])
+
+    def _lcccs_in(self, acc: dict):
+        """the LfLcccs over host copies of acc, and those copies (to be kept alive over the call)"""
+        from ._lib import LfLcccs, LfRingSlice
+        keep = {k: _u64(v) for k, v in acc.items()}
+        sl = lambda a: LfRingSlice(a.ctypes.data if a.size else None, a.size // self.d)
+        return LfLcccs(self.d, sl(keep["r"]), sl(keep["v"]), sl(keep["cm"]), sl(keep["u"]), sl(keep["x_w"]),
+                       keep["h"].ctypes.data), keep
+
+    @staticmethod
+    def _witness(w: dict):
+        from ._lib import LfWitness
+        return LfWitness(_dptr(w["w_ccs"]), _dptr(w["f"]), _dptr(w["f_coeff"]))
+
     def fold_prove(self, acc: dict, w_acc: dict, cm_i, x_ccs, w_i: dict, w_out: dict, repr: int = REPR_CANONICAL,
                    vars: bool = False):
         """acc: {r, v, cm, u, x_w, h} host arrays; w_*: {w_ccs, f, f_coeff} device tensors.
         Returns (folded LCCCS dict, LFProof dict) as host arrays; w_out is filled.
         vars=True: lf_fold_prove_vars, returning (LCCCS, LFProof, verification vars) with
         the vars replayed from the call's own sample log (keys as fold_replay's)."""
-        from ._lib import REPLAY_FIELDS, LfLcccs, LfLcccsMut, LfLfproofMut, LfReplayVars, LfRingSlice, LfWitness
+        from ._lib import REPLAY_FIELDS, LfLfproofMut, LfReplayVars
         d, s, tau, t, l, K, kappa = self.d, self.s, self.tau, self.t, self.l, self.pr.K, self.kappa
-        keep = {k: _u64(v) for k, v in acc.items()}
-        sl = lambda a: LfRingSlice(a.ctypes.data, a.size // d)
-        A = LfLcccs(d, sl(keep["r"]), sl(keep["v"]), sl(keep["cm"]), sl(keep["u"]), sl(keep["x_w"]),
-                    keep["h"].ctypes.data)
-        wit = lambda w: LfWitness(_dptr(w["w_ccs"]), _dptr(w["f"]), _dptr(w["f_coeff"]))
-        out = {"r": np.zeros(s * d, np.uint64), "v": np.zeros(tau * d, np.uint64),
-               "cm": np.zeros(kappa * d, np.uint64), "u": np.zeros(t * d, np.uint64),
-               "x_w": np.zeros(max(l, 1) * d, np.uint64), "h": np.zeros(d, np.uint64)}
+        A, keep = self._lcccs_in(acc)
+        out, O_ = self._lcccs_out()
         pf = {"lin_sumcheck": np.zeros(s * (self.degree + 2) * d, np.uint64), "lin_v": np.zeros(tau * d, np.uint64),
               "lin_u": np.zeros(t * d, np.uint64),
               "u_s": [np.zeros(K * t * d, np.uint64) for _ in range(2)],
@@ -798,7 +817,6 @@ class Prover:
               "y_s": [np.zeros(K * kappa * d, np.uint64) for _ in range(2)],
               "fold_sumcheck": np.zeros(s * (2 * self.pr.b_small + 1) * d, np.uint64),
               "theta_s": np.zeros(2 * K * tau * d, np.uint64), "eta_s": np.zeros(2 * K * t * d, np.uint64)}
-        O_ = LfLcccsMut(*[out[k].ctypes.data for k in ("r", "v", "cm", "u", "x_w", "h")])
         PM = LfLfproofMut()
         for k in ("lin_sumcheck", "lin_v", "lin_u", "fold_sumcheck", "theta_s", "eta_s"):
             setattr(PM, k, pf[k].ctypes.data)
@@ -807,7 +825,7 @@ class Prover:
                 getattr(PM, k)[side] = pf[k][side].ctypes.data
         cm = _u64(cm_i)
         xc = _u64(x_ccs) if l else np.zeros(1, np.uint64)
-        wa, wi, wo = wit(w_acc), wit(w_i), wit(w_out)
+        wa, wi, wo = self._witness(w_acc), self._witness(w_i), self._witness(w_out)
         if vars:
             vout = {k: np.zeros(n * d, np.uint64) for k, n in replay_sizes(self.pr, self.t, self.ccs.m, l, self.degree,
                                                                            len(self.S), kappa).items()}
@@ -818,7 +836,7 @@ class Prover:
             rc = self.lib.lf_fold_prove(self.h, C.byref(A), C.byref(wa), cm.ctypes.data, xc.ctypes.data, C.byref(wi),
                                         C.byref(O_), C.byref(wo), C.byref(PM), repr)
         if rc:
-            raise LfError(rc, self.lib.lf_prover_last_error(self.h).decode() or self.lib.lf_status_string(rc).decode())
+            self._raise(rc)
         out["x_w"] = out["x_w"][:l * d]
         return (out, pf, vout) if vars else (out, pf)
 
@@ -841,19 +859,15 @@ class Prover:
     def linearize(self, cm, x_ccs, w: dict, repr: int = REPR_CANONICAL):
         """initialize_accumulator's LFLinearizationProver::prove on a fresh transcript:
         -> (LCCCS dict, linearization sumcheck messages)"""
-        from ._lib import LfLcccsMut, LfWitness
-        d, s, tau, t, l = self.d, self.s, self.tau, self.t, self.l
-        out = {"r": np.zeros(s * d, np.uint64), "v": np.zeros(tau * d, np.uint64),
-               "cm": np.zeros(self.kappa * d, np.uint64), "u": np.zeros(t * d, np.uint64),
-               "x_w": np.zeros(max(l, 1) * d, np.uint64), "h": np.zeros(d, np.uint64)}
-        sc = np.zeros(s * (self.degree + 2) * d, np.uint64)
-        O_ = LfLcccsMut(*[out[k].ctypes.data for k in ("r", "v", "cm", "u", "x_w", "h")])
+        d, l = self.d, self.l
+        out, O_ = self._lcccs_out()
+        sc = np.zeros(self.s * (self.degree + 2) * d, np.uint64)
         cm, xc = _u64(cm), (_u64(x_ccs) if l else np.zeros(1, np.uint64))
-        wi = LfWitness(_dptr(w["w_ccs"]), _dptr(w["f"]), _dptr(w["f_coeff"]))
+        wi = self._witness(w)
         rc = self.lib.lf_linearize(self.h, cm.ctypes.data, xc.ctypes.data, C.byref(wi), C.byref(O_), sc.ctypes.data,
                                    repr)
         if rc:
-            raise LfError(rc, self.lib.lf_prover_last_error(self.h).decode() or self.lib.lf_status_string(rc).decode())
+            self._raise(rc)
         out["x_w"] = out["x_w"][:l * d]
         return out, sc
 
@@ -861,20 +875,15 @@ class Prover:
         if rc == 12:
             raise RelationError(failed, row if failed == REL_CCS else None)
         if rc:
-            raise LfError(rc, self.lib.lf_prover_last_error(self.h).decode() or self.lib.lf_status_string(rc).decode())
+            self._raise(rc)
         return norm
 
     def check_lcccs(self, acc: dict, w: dict, bound: int = 0, repr: int = REPR_CANONICAL) -> int:
         """does the device witness w = {w_ccs, f, f_coeff} open the LCCCS acc = {r, v, cm, u,
         x_w, h} (lf_lcccs_check)? Returns linf(f_coeff); RelationError names the first failed
         check. bound != 0: the norm must be below it."""
-        from ._lib import LfLcccs, LfRingSlice, LfWitness
-        d = self.d
-        keep = {k: _u64(v) for k, v in acc.items()}
-        sl = lambda a: LfRingSlice(a.ctypes.data if a.size else None, a.size // d)
-        A = LfLcccs(d, sl(keep["r"]), sl(keep["v"]), sl(keep["cm"]), sl(keep["u"]), sl(keep["x_w"]),
-                    keep["h"].ctypes.data)
-        wi = LfWitness(_dptr(w["w_ccs"]), _dptr(w["f"]), _dptr(w["f_coeff"]))
+        A, keep = self._lcccs_in(acc)
+        wi = self._witness(w)
         norm, failed = C.c_uint64(0), C.c_int(0)
         rc = self.lib.lf_lcccs_check(self.h, C.byref(A), C.byref(wi), bound, C.byref(norm), C.byref(failed), repr)
         return self._relation_result(rc, failed.value, -1, norm.value)
@@ -883,9 +892,8 @@ class Prover:
         """does the device witness w open the CCCS (cm, x_ccs) and satisfy the CCS
         (lf_cccs_check)? Returns linf(f_coeff); RelationError names the first failed check
         and, for the CCS relation, the first unsatisfied row."""
-        from ._lib import LfWitness
         cm, xc = _u64(cm), (_u64(x_ccs) if self.l else np.zeros(1, np.uint64))
-        wi = LfWitness(_dptr(w["w_ccs"]), _dptr(w["f"]), _dptr(w["f_coeff"]))
+        wi = self._witness(w)
         norm, failed, row = C.c_uint64(0), C.c_int(0), C.c_int64(-1)
         rc = self.lib.lf_cccs_check(self.h, cm.ctypes.data, xc.ctypes.data, C.byref(wi), bound, C.byref(norm),
                                     C.byref(failed), C.byref(row), repr)

@@ -102,6 +102,7 @@ struct lf_ctx {
   hipEvent_t cjoin = nullptr;   // the end of the last such contraction
   std::vector<TimedLaunch> pending;
   std::map<int, std::pair<double, long>> stats;  // nvec -> (ms, count)
+  ~lf_ctx();  // lf_api.hip: everything above, on `device`
 };
 
 // Every entry point runs on its context's device and restores the caller's

@@ -11,11 +11,18 @@
 // commitments, the Mz products, both sumchecks, the MLE evaluations, the fold),
 // the transcript stays on the host, and only the protocol's messages -- a few
 // hundred ring elements -- cross PCIe. The witnesses stay in HBM.
+// Layout: lf_prover and its construction (the CCS-structure analysis, the carved
+// allocations); Run (one call's stream, transcript and first error), GroupFeed (the
+// second host thread that enqueues instance groups) and Fold (what crosses the
+// phases of one call); lf_fold_prove as the table FOLD_PHASES of one function per
+// LF_SPAN_* span; lf_linearize and the two relation checks on the same helpers.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
 #include <chrono>
 #include <cstring>
+#include <memory>
+#include <optional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -31,15 +38,15 @@ struct lf_prover {
   // shape
   int d = 0, tb = 1, tau = 1, s = 0, K = 0, t = 0, q = 0, degree = 0, nm_lin = 0, nm_fold = 0;
   size_t W = 0, N = 0, n = 0, nn = 0, l = 0, kappa = 0;
-  std::vector<uint64_t> c;  // q NTT elements
+  std::vector<uint64_t> one;  // ONE (From<BaseRing> of 1): 1 in every NTT slot
+  std::vector<uint64_t> c;    // q NTT elements
   std::vector<int> S_off, S_idx;
   std::vector<int> lin_list;  // the matrix of every linearization MLE (c_i != 0, j in S_i)
   // the Mz MLEs are materialised live matrices first (mz_order: the matrices read by the
   // linearization's combination, then the others); S_live: each multiset entry's
-  // position among the nlive live ones; bad_S: a multiset index past the MLE list
+  // position among the nlive live ones
   std::vector<int> mz_order, S_live;
   int nlive = 0;
-  bool bad_S = false;
   // the linearization's round-0 points per multiset: b is active for S_i when every
   // factor's matrix has an entry in row 2b or 2b + 1 (lf_sumcheck_prove_lin_sparse);
   // act_off [q + 1] into the device list act
@@ -72,13 +79,11 @@ struct lf_prover {
   // ev[0], ev[1]: per-side / theta readiness; ev[2 + g]: instance group g's messages
   hipEvent_t ev[2 + 2 * 16] = {};
   ~lf_prover() {
-    int prev = -1;
-    if (hipGetDevice(&prev) == hipSuccess && prev != device) (void)hipSetDevice(device);
+    DevGuard g(device);
     if (mem) (void)hipFree(mem);
     if (pin) (void)hipHostFree(pin);
     for (auto &e : ev)
       if (e) (void)hipEventDestroy(e);
-    if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
   }
 };
 
@@ -92,6 +97,237 @@ constexpr int MZ_GROUP = 2;
 void broadcast(const uint64_t *base, int tb, int d, uint64_t *out) {
   for (int i = 0; i < d; i++) out[i] = base[i % tb];
 }
+
+int bad(lf_prover *P, int code, const char *msg) {
+  P->err = msg;
+  return code;
+}
+
+int hip_status(hipError_t e) { return e == hipErrorOutOfMemory ? LF_ERR_OUT_OF_MEMORY : LF_ERR_DEVICE; }
+
+bool repr_ok(int repr) { return repr == LF_REPR_CANONICAL || repr == LF_REPR_MONTGOMERY; }
+
+// a host copy of a public input in canonical form
+std::vector<uint64_t> canon(const uint64_t *src, size_t elems, int repr) {
+  std::vector<uint64_t> v(src, src + elems);
+  if (repr == LF_REPR_MONTGOMERY)
+    for (auto &x : v) x = gl::from_mont(x);
+  return v;
+}
+
+void to_mont(uint64_t *p, size_t elems) {
+  for (size_t i = 0; i < elems; i++) p[i] = gl::to_mont(p[i]);
+}
+
+void lcccs_to_mont(const lf_prover *P, lf_lcccs_mut *o) {
+  const size_t d = P->d;
+  to_mont(o->r, P->s * d);
+  to_mont(o->v, P->tau * d);
+  to_mont(o->cm, P->kappa * d);
+  to_mont(o->u, P->t * d);
+  to_mont(o->x_w, P->l * d);
+  to_mont(o->h, d);
+}
+
+bool lcccs_sizes_ok(const lf_prover *P, const lf_lcccs *a) {
+  return a->d == P->d && a->r.n == (size_t)P->s && a->v.n == (size_t)P->tau && a->cm.n == P->kappa &&
+         a->u.n == (size_t)P->t && a->x_w.n == P->l && a->h;
+}
+
+bool lcccs_out_ok(const lf_prover *P, const lf_lcccs_mut *o) {
+  return o->r && o->v && o->cm && o->u && (!P->l || o->x_w) && o->h;
+}
+
+// the witness buffers a call reads or writes: f_coeff always, f and w_ccs where asked for
+bool witness_ok(const lf_witness *w, bool f, bool w_ccs) { return w->f_coeff && (!f || w->f) && (!w_ccs || w->w_ccs); }
+
+struct TGuard {
+  lf_transcript *t;
+  ~TGuard() { lf_transcript_free(t); }
+};
+
+// ---------------------------------------------------------------- lf_prover_create's parts
+
+// the shape from the CCS, the Ajtai matrix and the parameters; LF_ERR_INVALID_ARG where
+// they do not fit one another
+int prover_shape(lf_prover *P) {
+  const lf_params *pr = &P->pr;
+  const int d = pr->d;
+  size_t m = 0, n = 0, l = 0;
+  int t = 0, q = 0, degree = 0;
+  if (lf_ccs_shape(P->ccs, &t, &m, &n, &l, &q, &degree) != LF_OK || q < 1)
+    return LF_ERR_INVALID_ARG;  // lf_ccs_set_structure first
+  if (lf_ajtai_d(P->aj) != d || (m & (m - 1)) || m < 2 || pr->b_small < 2 || pr->K < 1 || pr->K > 16 || pr->L < 1 ||
+      n < l + 2)
+    return LF_ERR_INVALID_ARG;
+  P->d = d;
+  P->tb = d == 24 ? 3 : 1;
+  P->tau = d == 24 ? 3 : 1;
+  P->K = pr->K;
+  P->t = t;
+  P->q = q;
+  P->degree = degree;
+  P->n = n;
+  P->l = l;
+  P->W = n - l - 1;
+  P->N = P->W * (size_t)pr->L;
+  P->nn = m;
+  while (((size_t)1 << P->s) < m) P->s++;
+  P->kappa = lf_ajtai_kappa(P->aj);
+  P->nm_fold = 5 + 2 * P->K * P->tau;
+  P->one.assign(d, 0);
+  for (int i = 0; i < d; i += P->tb) P->one[i] = 1;
+  // sanity_check (zk_latticefold.rs:152-158): m = max((n - l - 1) L, m).next_power_of_two();
+  // Witness::get_fhat gives MLEs of log2(N.next_power_of_two()) variables, which the
+  // sumchecks over s = log2 m variables need to be s as well
+  size_t want = std::max(P->N, m), pw = 1;
+  while (pw < want) pw <<= 1;
+  size_t npw = 1;
+  while (npw < P->N) npw <<= 1;
+  if (pw != m || npw != m || lf_ajtai_width(P->aj) != P->N)
+    return LF_ERR_INVALID_ARG;  // CSError::InvalidSizeBounds / a witness of another width
+  return LF_OK;
+}
+
+bool c_is_zero(const lf_prover *P, int i) {
+  bool zero = true;
+  for (int k = 0; k < P->d; k++) zero &= P->c[(size_t)i * P->d + k] == 0;
+  return zero;
+}
+
+// c, S and lin_list: the matrix behind every position of the linearization's MLE list
+void linearization_mle_list(lf_prover *P) {
+  const int q = P->q;
+  P->c.resize((size_t)q * P->d);
+  P->S_off.resize(q + 1);
+  lf_ccs_get_structure(P->ccs, P->c.data(), P->S_off.data(), nullptr);
+  P->S_idx.resize(P->S_off[q]);
+  lf_ccs_get_structure(P->ccs, nullptr, nullptr, P->S_idx.data());
+  for (int i = 0; i < q; i++) {
+    if (c_is_zero(P, i)) continue;  // prepare_lin_sumcheck_polynomial skips c_i = 0 (linearization/utils.rs:71-84)
+    for (int k = P->S_off[i]; k < P->S_off[i + 1]; k++) P->lin_list.push_back(P->S_idx[k]);
+  }
+  P->nm_lin = (int)P->lin_list.size() + 1;
+}
+
+// mz_order, S_live and nlive; rejects (message in the context's last error) a multiset
+// index that is no Mz MLE's list position
+int live_matrix_order(lf_prover *P) {
+  std::vector<int> pos_of(P->t, -1);
+  bool eq_slot = false;
+  P->S_live.resize(P->S_idx.size());
+  for (size_t k = 0; k < P->S_idx.size(); k++) {
+    const int p = P->S_idx[k];
+    if (p < 0 || (size_t)p > P->lin_list.size()) {
+      // past the eq(beta) slot or negative: malformed, the reference would panic on the index
+      lf_ctx_set_error(P->ctx, "lf_prover_create: a multiset index is negative or past the Mz MLE list and its "
+                               "eq(beta) slot");
+      return LF_ERR_INVALID_ARG;
+    }
+    if ((size_t)p == P->lin_list.size()) {
+      eq_slot = true;
+      continue;
+    }
+    const int j = P->lin_list[p];
+    if (pos_of[j] < 0) {
+      pos_of[j] = (int)P->mz_order.size();
+      P->mz_order.push_back(j);
+    }
+    P->S_live[k] = pos_of[j];
+  }
+  if (eq_slot) {
+    // The reference's list position lin_list.size() is the eq(beta) MLE itself
+    // (linearization/utils.rs:71-84): a multiset naming it would put a second eq
+    // factor into its term, which the split-eq sumcheck (eq(beta) taken out of every
+    // term) does not express. Rejected here, by name, rather than mid-fold.
+    lf_ctx_set_error(P->ctx, "lf_prover_create: a multiset index is the position of eq(beta) in the MLE list; "
+                             "multisets over eq(beta) are not supported");
+    return LF_ERR_UNSUPPORTED_CCS;
+  }
+  P->nlive = (int)P->mz_order.size();
+  for (int j = 0; j < P->t; j++)
+    if (pos_of[j] < 0) P->mz_order.push_back(j);
+  return LF_OK;
+}
+
+// act_off and act_host: the linearization's active round-0 points of every multiset
+void active_points(lf_prover *P) {
+  const size_t m = P->nn, half = m / 2;
+  std::vector<uint8_t> row(m);
+  std::vector<std::vector<uint8_t>> pair(P->nlive, std::vector<uint8_t>(half));
+  for (int i = 0; i < P->nlive; i++) {
+    lf_ccs_row_live(P->ccs, P->mz_order[i], row.data());
+    for (size_t b = 0; b < half; b++) pair[i][b] = row[2 * b] | row[2 * b + 1];
+  }
+  P->act_off.assign(P->q + 1, 0);
+  for (int i = 0; i < P->q; i++) {
+    if (!c_is_zero(P, i))  // c_i = 0: no active point
+      for (size_t b = 0; b < half; b++) {
+        bool on = true;
+        for (int k = P->S_off[i]; k < P->S_off[i + 1] && on; k++) on = pair[P->S_live[k]][b];
+        if (on) P->act_host.push_back((uint32_t)b);
+      }
+    P->act_off[i + 1] = (uint32_t)P->act_host.size();
+  }
+}
+
+// One allocation carved into parts, each rounded up to `align` elements: the total,
+// and with a base where every part starts
+struct Part {
+  uint64_t **p;
+  size_t elems;
+};
+size_t carve(const std::vector<Part> &parts, size_t align, uint64_t *base) {
+  size_t off = 0;
+  for (auto &x : parts) {
+    if (base) *x.p = base + off;
+    off += (x.elems + align - 1) / align * align;
+  }
+  return off;
+}
+
+// the device memory, the round-0 point list in it, the pinned staging and the events
+int prover_alloc(lf_prover *P) {
+  const size_t d = P->d, K = P->K, N = P->N, W = P->W, n = P->n, nn = P->nn, l = P->l, kd = P->kappa * d, tau = P->tau,
+               t = P->t, s = P->s;
+  const std::vector<Part> parts = {
+      {&P->z, n * d}, {&P->mz, t * nn * d}, {&P->lin, (size_t)std::max(P->nlive, 1) * std::max<size_t>(nn / 4, 1) * d},
+      {&P->pt, s * d}, {&P->beta, s * d}, {&P->val, (t + 3) * d},
+      {&P->fkc[0], K * N * d}, {&P->fkc[1], K * N * d}, {&P->fk[0], K * N * d}, {&P->fk[1], K * N * d},
+      {&P->wk[0], K * W * d}, {&P->wk[1], K * W * d}, {&P->y[0], K * kd}, {&P->y[1], K * kd},
+      {&P->cmd[0], kd}, {&P->cmd[1], kd}, {&P->xw[0], (l + 1) * d}, {&P->xw[1], (l + 1) * d},
+      {&P->xs, 2 * K * (l + 1) * d}, {&P->zdec[0], K * n * d}, {&P->zdec[1], K * n * d},
+      {&P->vs, 2 * K * tau * d}, {&P->us, 2 * K * t * d}, {&P->fold, (size_t)P->nm_fold * nn * d},
+      {&P->coef[0], K * tau * d}, {&P->coef[1], K * tau * d}, {&P->zeta, 2 * K * d}, {&P->mu, 2 * K * d},
+      {&P->theta, 2 * K * tau * d}, {&P->eta, 2 * K * t * d}, {&P->rho, 2 * K * d}, {&P->rhoc, 2 * K * d},
+      {&P->cm0, kd}, {&P->u0, t * d}, {&P->x0, (l + 1) * d}, {&P->v0, tau * d}, {&P->r0, s * d},
+      {&P->eq0, nn * d}, {&P->mzw, lf_ccs_weights_len(P->ccs)}, {&P->lev, t * d},
+      {&P->chk, 2}, {reinterpret_cast<uint64_t **>(&P->act), (P->act_host.size() + 1) / 2}};
+  const std::vector<Part> pins = {
+      {&P->hx[0], K * (l + 1) * d}, {&P->hx[1], K * (l + 1) * d}, {&P->hy[0], K * kd}, {&P->hy[1], K * kd},
+      {&P->hu[0], K * t * d}, {&P->hu[1], K * t * d}, {&P->hv[0], K * tau * d}, {&P->hv[1], K * tau * d},
+      {&P->hr[0], s * d}, {&P->hr[1], s * d}, {&P->htheta, 2 * K * tau * d}, {&P->heta, 2 * K * t * d}};
+  DevGuard g(P->device);
+  hipError_t e = hipMalloc(&P->mem, carve(parts, 32, nullptr) * 8);  // 256-B aligned parts
+  if (e != hipSuccess) {
+    P->mem = nullptr;
+    return hip_status(e);
+  }
+  carve(parts, 32, P->mem);
+  if (!P->act_host.empty()) {
+    if (hipMemcpy(P->act, P->act_host.data(), P->act_host.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+      return LF_ERR_DEVICE;
+    P->act_host = std::vector<uint32_t>();
+  }
+  e = hipHostMalloc(reinterpret_cast<void **>(&P->pin), carve(pins, 8, nullptr) * 8, hipHostMallocDefault);
+  for (auto &ev : P->ev)
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+  if (e != hipSuccess) return hip_status(e);
+  carve(pins, 8, P->pin);
+  return LF_OK;
+}
+
+// ---------------------------------------------------------------- one call's state
 
 struct Run {
   lf_prover *P;
@@ -122,7 +358,7 @@ struct Run {
   }
   int hip(hipError_t e, const char *what) {
     if (e != hipSuccess && rc == LF_OK) {
-      rc = e == hipErrorOutOfMemory ? LF_ERR_OUT_OF_MEMORY : LF_ERR_DEVICE;
+      rc = hip_status(e);
       errs() = std::string(what) + ": " + hipGetErrorString(e);
     }
     return rc;
@@ -167,25 +403,96 @@ struct Run {
     }
     return out;
   }
+  // the sumcheck's point (one base-ring challenge per round) as NTT elements
+  std::vector<uint64_t> point(const std::vector<uint64_t> &rnd) {
+    std::vector<uint64_t> r((size_t)P->s * P->d);
+    for (int i = 0; i < P->s; i++) broadcast(rnd.data() + (size_t)i * P->tb, P->tb, P->d, r.data() + (size_t)i * P->d);
+    return r;
+  }
 };
+
+// Instance groups go to the device from a second host thread: with the stream's queue
+// deep, every enqueue blocks the calling thread for tens of microseconds, which the
+// transcript thread would otherwise spend before and between its absorbs. The body
+// enqueues on Q -- a Run of the feed's own, so the error state is not shared and P->err
+// is never written from two threads -- and calls post(g) once group g's event
+// P->ev[2 + g] is recorded; the transcript thread calls wait(R, g) before it reads
+// group g's messages, and join(R) when it has read them all. Where no thread is to be
+// had the body runs in the constructor (everything enqueued first); the destructor
+// joins, so no return path leaves a thread behind.
+class GroupFeed {
+  static constexpr int DONE = 1 << 30;
+  std::atomic<int> posted{0};  // groups whose event is recorded; DONE: the body has returned (also on an error)
+  std::string err;             // the body's own error text, merged into R's by join
+  std::thread th;
+
+ public:
+  Run Q;
+  template <class Body>
+  GroupFeed(const Run &R, Body body) : Q(R) {
+    Q.err = &err;
+    auto work = [this, body] {
+      DevGuard g(Q.P->device);  // a new thread starts on device 0
+      if (Q.rc == LF_OK) body(*this);
+      posted.store(DONE, std::memory_order_release);
+    };
+    try {
+      th = std::thread(work);
+    } catch (const std::exception &) {
+      work();
+    }
+  }
+  ~GroupFeed() {
+    if (th.joinable()) th.join();
+  }
+  void post(int g) { posted.store(g + 1, std::memory_order_release); }
+  // nonzero: the body or the wait failed, and the caller returns join(R)
+  int wait(Run &R, int g) {
+    while (posted.load(std::memory_order_acquire) <= g) std::this_thread::yield();
+    if (posted.load(std::memory_order_acquire) >= DONE && Q.rc != LF_OK) return Q.rc;
+    return R.wait(R.P->ev[2 + g]);
+  }
+  int join(Run &R) {
+    if (th.joinable()) th.join();
+    if (Q.rc != LF_OK && R.rc == LF_OK) {
+      R.rc = Q.rc;
+      R.errs() = err;
+    }
+    return R.rc;
+  }
+};
+
+// what crosses the phases of one lf_fold_prove
+struct Fold {
+  const lf_witness *w_acc, *w_i, *w_out;
+  lf_lcccs_mut *out;
+  lf_lfproof_mut *proof;
+  // host copies of the public inputs in canonical form: the accumulator's r, v, cm, u, x_w, h; cm_i, x_ccs
+  std::vector<uint64_t> ar, av, acm, au, axw, ah, cmi, xc;
+  std::vector<uint64_t> r_lin, lv, lu;  // the linearized instance: {r, v, cm_i, u, x_ccs, h = ONE}
+  std::vector<uint64_t> r0;             // the folding sumcheck's point
+  std::vector<uint64_t> rhoc;           // the rho_s' coefficients
+  std::vector<uint64_t> x0;             // x_0 = x_w || h of the folded instance
+  lf_fold_step_bufs b{};                // the decomposition's buffers, which the fold completes
+  // the folding MLEs [eq(r_0), g1, eq(r_1), g3, eq(beta), f_hat (2K x tau)], mstride words apart
+  uint64_t *M = nullptr;
+  size_t mstride = 0;
+  int ng = 0;           // instance groups per side
+  bool digits = false;  // B_SMALL = 2, f_hat values in {-1, 0, 1}: read from the coefficient rows
+  std::optional<GroupFeed> feed;  // declared last: joined before anything its body reads goes away
+};
+
+// ---------------------------------------------------------------- linearization
 
 // z = x_ccs || 1 || w_ccs (Instance::get_z_vector) and its Mz MLEs: independent of the
 // transcript, so enqueued before the public input is absorbed (the device computes
 // them while the host hashes). Live matrices first (lf_prover::mz_order).
 int linearize_prepare(lf_prover *P, Run &R, const std::vector<uint64_t> &xc, const lf_witness *w_i) {
-  lf_ctx *C = P->ctx;
-  const int d = P->d, tb = P->tb;
-  const size_t W = P->W, l = P->l;
-  if (P->bad_S) {
-    P->err = "multiset index past the MLE list";
-    return R.rc = LF_ERR_INVALID_ARG;
-  }
-  std::vector<uint64_t> one(d, 0);
-  for (int i = 0; i < d; i += tb) one[i] = 1;
-  R.h2d(P->z, xc.data(), l * d);
-  R.h2d(P->z + l * d, one.data(), d);
-  R.d2d(P->z + (l + 1) * d, w_i->w_ccs, W * d);
-  return R.check(lf_dev_mz_mles_sel(C, P->ccs, P->z, P->mz_order.data(), P->t, P->s, P->mz), "Mz MLEs");
+  const int d = P->d;
+  R.h2d(P->z, xc.data(), P->l * d);
+  R.h2d(P->z + P->l * d, P->one.data(), d);
+  R.d2d(P->z + (P->l + 1) * d, w_i->w_ccs, P->W * d);
+  return R.check(lf_dev_mz_mles_sel(P->ctx, P->ccs, P->z, P->mz_order.data(), P->t, P->s, P->mz), "Mz MLEs");
 }
 
 // LFLinearizationProver::prove (linearization.rs:153-197) of the CCCS (cm, x_ccs)
@@ -221,8 +528,7 @@ int linearize(lf_prover *P, Run &R, const lf_witness *w_i, uint64_t *lin_sumchec
               "linearization sumcheck");
   }
   if (R.rc) return R.rc;
-  r_lin.assign((size_t)s * d, 0);
-  for (int i = 0; i < s; i++) broadcast(rnd.data() + (size_t)i * tb, tb, d, r_lin.data() + (size_t)i * d);
+  r_lin = R.point(rnd);
   R.h2d(P->pt, r_lin.data(), (size_t)s * d);
   // v = f_hat(w_i) at r, u = MLE(M_j z)(r) (compute_evaluation_vectors, :130-147): the
   // live matrices' u are the sumcheck's final values, the others are evaluated against
@@ -249,21 +555,304 @@ int linearize(lf_prover *P, Run &R, const lf_witness *w_i, uint64_t *lin_sumchec
   return LF_OK;
 }
 
-int bad(lf_prover *P, int code, const char *msg) {
-  P->err = msg;
-  return code;
+// ---------------------------------------------------------------- the phases of lf_fold_prove
+// One function per LF_SPAN_* span, in protocol order (FOLD_PHASES below); each returns
+// nonzero to end the call with that status.
+
+// absorb_public_input (zk_latticefold.rs:162-184)
+int public_input(lf_prover *P, Run &R, Fold &F) {
+  // the linearization's Mz MLEs need no challenge: on the device while the host absorbs
+  if (linearize_prepare(P, R, F.xc, F.w_i)) return R.rc;
+  R.absorb_label("acc");
+  R.absorb(F.ar.data(), P->s);
+  R.absorb(F.av.data(), P->tau);
+  R.absorb(F.acm.data(), P->kappa);
+  R.absorb(F.au.data(), P->t);
+  R.absorb(F.axw.data(), P->l);
+  R.absorb(F.ah.data(), 1);
+  R.absorb_label("cm_i");
+  R.absorb(F.cmi.data(), P->kappa);
+  R.absorb(F.xc.data(), P->l);
+  return LF_OK;
 }
 
-// restores the calling thread's device on scope exit
-struct OnDevice {
-  int prev = -1, dev;
-  explicit OnDevice(int device) : dev(device) {
-    if (hipGetDevice(&prev) == hipSuccess && prev != dev) (void)hipSetDevice(dev);
+// linearization (linearization.rs:153-197)
+int linearization(lf_prover *P, Run &R, Fold &F) {
+  return linearize(P, R, F.w_i, F.proof->lin_sumcheck, F.r_lin, F.lv, F.lu);
+}
+
+// one side's v_s and u_s at its point r_i, and its messages back to pinned memory
+void enqueue_decomposed_side(lf_prover *P, GroupFeed &E, const Fold &F, int side) {
+  lf_ctx *C = P->ctx;
+  Run &Q = E.Q;
+  const int d = P->d, tau = P->tau, s = P->s, K = P->K, t = P->t, G = MZ_GROUP;
+  const size_t N = P->N, n = P->n, l = P->l, kd = P->kappa * d;
+  const uint64_t *eq_s = F.M + (size_t)(2 * side) * F.mstride;
+  Q.check(lf_dev_fhat_evaluate_eq(C, d, P->fkc[side], N, N * d, K, s, eq_s, P->vs + (size_t)side * K * tau * d), "v_s");
+  Q.d2p(P->hx[side], P->xs + (size_t)side * K * (l + 1) * d, (size_t)K * (l + 1) * d);
+  Q.d2p(P->hy[side], P->y[side], (size_t)K * kd);
+  Q.d2p(P->hv[side], P->vs + (size_t)side * K * tau * d, (size_t)K * tau * d);
+  Q.check(lf_dev_mz_weights(C, P->ccs, s, eq_s, P->mzw), "u_s weights");
+  for (int g = 0; g < F.ng; g++) {
+    const int k0 = g * G, nk = std::min(G, K - k0);
+    uint64_t *us = P->us + ((size_t)side * K + k0) * t * d;
+    Q.check(lf_dev_mz_dots(C, P->ccs, P->mzw, P->zdec[side] + (size_t)k0 * n * d, nk, us), "u_s");
+    Q.d2p(P->hu[side] + (size_t)k0 * t * d, us, (size_t)nk * t * d);
+    Q.hip(hipEventRecord(P->ev[2 + side * F.ng + g], Q.st), "event");
+    E.post(side * F.ng + g);
   }
-  ~OnDevice() {
-    if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
+}
+
+// the two decompositions (decomposition.rs:33-88), device work of both first
+int decomposition(lf_prover *P, Run &R, Fold &F) {
+  lf_ctx *C = P->ctx;
+  const int d = P->d, s = P->s, K = P->K;
+  const size_t W = P->W, l = P->l, kd = P->kappa * d;
+  R.h2d(P->cmd[0], F.acm.data(), kd);
+  R.h2d(P->cmd[1], F.cmi.data(), kd);
+  R.h2d(P->xw[0], F.axw.data(), l * d);  // x_w || h of each side
+  R.h2d(P->xw[0] + l * d, F.ah.data(), d);
+  R.h2d(P->xw[1], F.xc.data(), l * d);
+  R.h2d(P->xw[1] + l * d, P->one.data(), d);
+  for (int side = 0; side < 2; side++)
+    R.check(lf_dev_compute_x_s(C, &P->pr, P->xw[side], l + 1, P->xs + (size_t)side * K * (l + 1) * d), "compute_x_s");
+  lf_fold_step_bufs &b = F.b;
+  b.acc_f_coeff = F.w_acc->f_coeff;
+  b.f_coeff = const_cast<uint64_t *>(F.w_i->f_coeff);
+  b.acc_cm = P->cmd[0];
+  b.cm = P->cmd[1];
+  for (int side = 0; side < 2; side++) {
+    b.fk_coeff[side] = P->fkc[side];
+    b.fk[side] = P->fk[side];
+    b.wk[side] = P->wk[side];
+    b.y[side] = P->y[side];
   }
-};
+  if (R.rc == LF_OK) R.check(lf_dev_decompose_commit(C, P->aj, &P->pr, W, &b), "decompose + commit_witnesses");
+  // z_k = x_s[k] || w_ccs_k (compute_mz_mles, :229-256) for the u_s (and later eta_s), one
+  // launch per side (the stream's queue holds a bounded number of commands: every one
+  // saved is host time the transcript gets back)
+  for (int side = 0; side < 2; side++)
+    R.hip(lfk::assemble_z(P->xs + (size_t)side * K * (l + 1) * d, P->wk[side], K, l + 1, W, d, P->zdec[side], R.st),
+          "z_k");
+  // per side: v_s, u_s at the side's point, then its messages back to pinned memory
+  // behind events, so the host absorbs while the device evaluates: x_s, y_s and v_s
+  // of a side first, then u_s in groups of MZ_GROUP instances (one event each: the
+  // host starts on instance 0 as soon as its u_s is back), and the challenge-
+  // independent folding MLEs (the f_hat MLEs of the 2K decomposed witnesses, eq(r_i);
+  // create_sumcheck_polynomial, folding/utils.rs:196-255) behind them
+  // eq(r_i) of each side is the folding prover's eq(r_i) MLE (M slots 0 and 2; the
+  // linearization left eq(r_lin) in slot 2): v_s and u_s read it from there
+  R.h2p2d(P->pt, P->hr[0], F.ar.data(), (size_t)s * d);
+  R.check(lf_dev_eq_table(C, d, P->pt, s, F.M), "eq(r_0)");
+  F.feed.emplace(R, [P, &F](GroupFeed &E) {
+    enqueue_decomposed_side(P, E, F, 0);
+    enqueue_decomposed_side(P, E, F, 1);
+    if (!F.digits)
+      for (int sd = 0; sd < 2; sd++)
+        E.Q.hip(lfk::get_fhat(P->fkc[sd], P->N, P->d, P->s, F.M + (5 + (size_t)sd * P->K * P->tau) * F.mstride, E.Q.st,
+                              P->K, P->N * P->d),
+                "f_hat");
+  });
+  return LF_OK;
+}
+
+// the decomposed instances' messages (:58-64), each group once its event has fired
+int decomposition_transcript(lf_prover *P, Run &R, Fold &F) {
+  const int d = P->d, tau = P->tau, K = P->K, t = P->t;
+  const size_t l = P->l, kappa = P->kappa, kd = kappa * d;
+  lf_lfproof_mut *proof = F.proof;
+  for (int side = 0; side < 2; side++)
+    for (int k = 0; k < K; k++) {
+      if (k % MZ_GROUP == 0 && F.feed->wait(R, side * F.ng + k / MZ_GROUP)) return F.feed->join(R);
+      const size_t ox = (size_t)k * (l + 1) * d, oy = (size_t)k * kd, ou = (size_t)k * t * d, ov = (size_t)k * tau * d;
+      memcpy(proof->x_s[side] + ox, P->hx[side] + ox, (l + 1) * d * 8);
+      memcpy(proof->y_s[side] + oy, P->hy[side] + oy, kd * 8);
+      memcpy(proof->u_s[side] + ou, P->hu[side] + ou, (size_t)t * d * 8);
+      memcpy(proof->v_s[side] + ov, P->hv[side] + ov, (size_t)tau * d * 8);
+      R.absorb(proof->x_s[side] + ox, l + 1);
+      R.absorb(proof->y_s[side] + oy, kappa);
+      R.absorb(proof->u_s[side] + ou, t);
+      R.absorb(proof->v_s[side] + ov, tau);
+    }
+  return F.feed->join(R);
+}
+
+// folding (folding.rs:42-130): its challenges and the MLEs that depend on them
+int folding_mles(lf_prover *P, Run &R, Fold &F) {
+  lf_ctx *C = P->ctx;
+  const int d = P->d, tb = P->tb, tau = P->tau, s = P->s, K = P->K;
+  const size_t N = P->N, mstride = F.mstride;
+  uint64_t *M = F.M;
+  R.absorb_label("alpha_s");  // squeeze_alpha_beta_zeta_mu (folding/utils.rs:51-96)
+  const std::vector<uint64_t> alpha = R.challenges(2 * K);
+  R.absorb_label("zeta_s");
+  const std::vector<uint64_t> zeta = R.challenges(2 * K);
+  R.absorb_label("mu_s");
+  std::vector<uint64_t> mu = R.challenges(2 * K - 1);
+  mu.insert(mu.end(), P->one.begin(), P->one.end());
+  R.absorb_label("beta_s");
+  const std::vector<uint64_t> fbeta = R.challenges(s);
+  R.h2d(P->zeta, zeta.data(), 2 * (size_t)K * d);
+  R.h2d(P->mu, mu.data(), 2 * (size_t)K * d);
+  R.h2d(P->beta, fbeta.data(), (size_t)s * d);
+  // Horner weights alpha_k^(j+1) of each side's f_hat MLEs (prepare_g1_and_3_k_mles_list, :519-541)
+  for (int side = 0; side < 2; side++) {
+    std::vector<uint64_t> cf((size_t)K * tau * d);
+    for (int k = 0; k < K; k++) {
+      const uint64_t *a = alpha.data() + (size_t)(side * K + k) * d;  // broadcast: slot 0 holds the base value
+      uint64_t pw[3] = {a[0], tb == 3 ? a[1] : 0, tb == 3 ? a[2] : 0};
+      for (int j = 0; j < tau; j++) {
+        broadcast(pw, tb, d, cf.data() + ((size_t)k * tau + j) * d);
+        uint64_t nx[3];
+        gl::base_mul(pw, a, nx, tb);
+        memcpy(pw, nx, sizeof(pw));
+      }
+    }
+    R.h2d(P->coef[side], cf.data(), cf.size());
+  }
+  // the MLEs [eq(r_0), g1, eq(r_1), g3, eq(beta), f_hat (2K x tau)] (create_sumcheck_polynomial,
+  // :196-255): eq(r_i) were enqueued before the decomposition transcript; the f_hat MLEs
+  // (Witness::get_fhat of the decomposed witnesses) are not materialised for B_SMALL = 2 --
+  // their values are the digits of the coefficient rows P->fkc, which g1 / g3 and the
+  // sumcheck's first round read directly (lf_sumcheck_prove_fold_digits)
+  // both sides' challenged Mz MLEs in one pass over the matrices (g1, g3 slots)
+  R.check(lf_dev_mz_challenged_pair(C, P->ccs, P->zdec[0], P->zeta, P->zdec[1], P->zeta + (size_t)K * d, K, s,
+                                    M + mstride, M + 3 * mstride),
+          "challenged Mz");
+  for (int side = 0; side < 2; side++) {
+    uint64_t *g = M + (size_t)(2 * side + 1) * mstride;
+    if (F.digits)
+      R.hip(lfk::fhat_lincomb_digits(P->fkc[side], K, N, N * d, P->coef[side], s, d, g, R.st), "g");
+    else
+      R.check(lf_dev_mle_lincomb(C, d, M + (5 + (size_t)side * K * tau) * mstride, mstride, K * tau, s, P->coef[side], g),
+              "g");
+  }
+  R.check(lf_dev_eq_table(C, d, P->beta, s, M + 4 * mstride), "eq(beta)");
+  return LF_OK;
+}
+
+int folding_sumcheck(lf_prover *P, Run &R, Fold &F) {
+  const int d = P->d, s = P->s, K = P->K;
+  const size_t N = P->N;
+  std::vector<uint64_t> rnd((size_t)s * P->tb);
+  lf_comb cb{};
+  cb.kind = LF_COMB_FOLDING;
+  cb.nk = 2 * K;
+  cb.tau = P->tau;
+  cb.bsmall = (int)P->pr.b_small;
+  cb.mu = P->mu;
+  if (R.rc == LF_OK)
+    R.check(F.digits ? lf_sumcheck_prove_fold_digits(P->ctx, R.T, &cb, F.M, P->fkc[0], P->fkc[1], K, N, N * d, s, d,
+                                                     F.M + 5 * F.mstride, F.proof->fold_sumcheck, rnd.data())
+                     : lf_sumcheck_prove(P->ctx, R.T, &cb, F.M, P->nm_fold, s, d, 2 * cb.bsmall, F.proof->fold_sumcheck,
+                                         rnd.data()),
+            "folding sumcheck");
+  if (R.rc == LF_OK) F.r0 = R.point(rnd);
+  return R.rc;
+}
+
+// theta_s = f_hat(w_i)(r_0), eta_s = MLE(M_j z_i)(r_0) (get_thetas / get_etas, :236-256):
+// theta_s and side 0's eta_s come back first, so the host absorbs them while the
+// device evaluates side 1's eta_s
+int evaluations(lf_prover *P, Run &R, Fold &F) {
+  lf_ctx *C = P->ctx;
+  const int d = P->d, tau = P->tau, s = P->s, K = P->K;
+  const size_t N = P->N;
+  R.h2d(P->r0, F.r0.data(), (size_t)s * d);
+  // one eq(r_0) table and one set of Mz weights at r_0 for both sides
+  R.check(lf_dev_eq_table(C, d, P->r0, s, P->eq0), "eq(r_0)");
+  for (int side = 0; side < 2; side++)
+    R.check(lf_dev_fhat_evaluate_eq(C, d, P->fkc[side], N, N * d, K, s, P->eq0, P->theta + (size_t)side * K * tau * d),
+            "theta");
+  R.d2p(P->htheta, P->theta, 2 * (size_t)K * tau * d);
+  R.hip(hipEventRecord(P->ev[0], R.st), "event");
+  R.check(lf_dev_mz_weights(C, P->ccs, s, P->eq0, P->mzw), "eta weights");
+  if (R.rc) return R.rc;
+  // the eta_s groups of both sides from a second host thread, as the u_s groups
+  F.feed.emplace(R, [P, &F](GroupFeed &E) {
+    Run &Q = E.Q;
+    const int K = P->K, G = MZ_GROUP;
+    const size_t td = (size_t)P->t * P->d;
+    for (int side = 0; side < 2 && Q.rc == LF_OK; side++)
+      for (int gg = 0; gg < F.ng; gg++) {  // instance groups in absorb order
+        const int g = side * F.ng + gg, k0 = gg * G, nk = std::min(G, K - k0);
+        const size_t o = ((size_t)side * K + k0) * td;
+        Q.check(lf_dev_mz_dots(P->ctx, P->ccs, P->mzw, P->zdec[side] + (size_t)k0 * P->n * P->d, nk, P->eta + o),
+                "eta");
+        Q.d2p(P->heta + o, P->eta + o, (size_t)nk * td);
+        Q.hip(hipEventRecord(P->ev[2 + g], Q.st), "event");
+        E.post(g);
+      }
+  });
+  return LF_OK;
+}
+
+// theta_s and eta_s into the transcript as they arrive, then the rho_s
+int folding_transcript(lf_prover *P, Run &R, Fold &F) {
+  const int d = P->d, tau = P->tau, K = P->K, t = P->t;
+  lf_lfproof_mut *proof = F.proof;
+  if (R.wait(P->ev[0])) return F.feed->join(R);
+  memcpy(proof->theta_s, P->htheta, 2 * (size_t)K * tau * d * 8);
+  for (int i = 0; i < 2 * K; i++) R.absorb(proof->theta_s + (size_t)i * tau * d, tau);
+  for (int side = 0; side < 2; side++)
+    for (int k = 0; k < K; k++) {
+      if (k % MZ_GROUP == 0 && F.feed->wait(R, side * F.ng + k / MZ_GROUP)) return F.feed->join(R);
+      const size_t o = ((size_t)side * K + k) * t * d;
+      memcpy(proof->eta_s + o, P->heta + o, (size_t)t * d * 8);
+      R.absorb(proof->eta_s + o, t);
+    }
+  if (F.feed->join(R)) return R.rc;
+  // get_rhos (folding/utils.rs:116-127): 2K - 1 short challenges and ONE, then CRT
+  R.absorb_label("rho_s");
+  F.rhoc.assign(2 * (size_t)K * d, 0);
+  if (lf_transcript_get_short_challenges(R.T, d, 2 * K - 1, F.rhoc.data()) != LF_OK)
+    return bad(P, LF_ERR_CHALLENGE_BYTES, "short challenges");
+  F.rhoc[(size_t)(2 * K - 1) * d] = 1;
+  return LF_OK;
+}
+
+// f_0, cm_0, Witness::from_f(f_0) (:112-122), then v_0, u_0, x_0 (compute_v0_u0_x0_cm_0, :456-517)
+int fold_and_outputs(lf_prover *P, Run &R, Fold &F) {
+  lf_ctx *C = P->ctx;
+  const int d = P->d, K = P->K, t = P->t;
+  const size_t l = P->l;
+  R.h2d(P->rhoc, F.rhoc.data(), F.rhoc.size());
+  R.d2d(P->rho, P->rhoc, F.rhoc.size());
+  R.check(lf_dev_crt(C, P->rho, 2 * K, d), "CRT(rho)");
+  lf_fold_step_bufs &b = F.b;
+  b.rho = P->rho;
+  b.f0 = F.w_out->f;
+  b.f0_coeff = F.w_out->f_coeff;
+  b.w_ccs0 = F.w_out->w_ccs;
+  b.cm0 = P->cm0;
+  if (R.rc == LF_OK) R.check(lf_dev_fold_combine(C, P->aj, &P->pr, P->W, &b), "fold");
+  R.check(lf_dev_fold_lcccs(C, d, 2 * K, P->rho, P->rhoc, P->eta, t, P->xs, l + 1, P->theta, P->u0, P->x0, P->v0),
+          "v_0, u_0, x_0");
+  if (R.rc) return R.rc;
+  // prepare_public_output (folding.rs:381-392): x_w = x_0[..l], h = x_0[l]
+  F.x0.resize((l + 1) * d);
+  R.d2h(F.out->cm, P->cm0, P->kappa * d);
+  R.d2h(F.out->u, P->u0, (size_t)t * d);
+  R.d2h(F.out->v, P->v0, (size_t)P->tau * d);
+  R.d2h(F.x0.data(), P->x0, (l + 1) * d);
+  R.check(lf_ctx_sync(C), "sync");
+  return R.rc;
+}
+
+// the phases in protocol order, each with the span it closes; sync = false: see Run::mark
+constexpr struct {
+  int (*run)(lf_prover *, Run &, Fold &);
+  int span;
+  bool sync;
+} FOLD_PHASES[] = {{public_input, LF_SPAN_PUBLIC_INPUT, false},
+                   {linearization, LF_SPAN_LINEARIZATION, true},
+                   {decomposition, LF_SPAN_DECOMPOSITION, false},
+                   {decomposition_transcript, LF_SPAN_DECOMPOSITION_TRANSCRIPT, false},
+                   {folding_mles, LF_SPAN_FOLDING_MLES, true},
+                   {folding_sumcheck, LF_SPAN_FOLDING_SUMCHECK, true},
+                   {evaluations, LF_SPAN_EVALUATIONS, false},
+                   {folding_transcript, LF_SPAN_FOLDING_TRANSCRIPT, true},
+                   {fold_and_outputs, LF_SPAN_FOLD, true}};
 
 // The checks a witness answers for on its own and against its commitment, shared by
 // lf_lcccs_check and lf_cccs_check: LF_REL_WITNESS_F, _W (Witness::from_f of f against
@@ -313,188 +902,18 @@ extern "C" {
 int lf_prover_create(lf_ctx *ctx, const lf_ajtai *aj, const lf_params *pr, const lf_ccs *ccs, lf_prover **out) {
   if (!ctx || !aj || !pr || !ccs || !out) return LF_ERR_INVALID_ARG;
   *out = nullptr;
-  auto P = new lf_prover;
+  auto P = std::make_unique<lf_prover>();
   P->ctx = ctx;
   P->aj = aj;
   P->ccs = ccs;
   P->pr = *pr;
   P->device = lf_ctx_device(ctx);
-  const int d = pr->d;
-  size_t m = 0, n = 0, l = 0;
-  int t = 0, q = 0, degree = 0;
-  if (lf_ccs_shape(ccs, &t, &m, &n, &l, &q, &degree) != LF_OK || q < 1) {
-    delete P;
-    return LF_ERR_INVALID_ARG;  // lf_ccs_set_structure first
-  }
-  if (lf_ajtai_d(aj) != d || (m & (m - 1)) || m < 2 || pr->b_small < 2 || pr->K < 1 || pr->K > 16 || pr->L < 1 ||
-      n < l + 2) {
-    delete P;
-    return LF_ERR_INVALID_ARG;
-  }
-  P->d = d;
-  P->tb = d == 24 ? 3 : 1;
-  P->tau = d == 24 ? 3 : 1;
-  P->K = pr->K;
-  P->t = t;
-  P->q = q;
-  P->degree = degree;
-  P->n = n;
-  P->l = l;
-  P->W = n - l - 1;
-  P->N = P->W * (size_t)pr->L;
-  P->nn = m;
-  while (((size_t)1 << P->s) < m) P->s++;
-  P->kappa = lf_ajtai_kappa(aj);
-  // sanity_check (zk_latticefold.rs:152-158): m = max((n - l - 1) L, m).next_power_of_two();
-  // Witness::get_fhat gives MLEs of log2(N.next_power_of_two()) variables, which the
-  // sumchecks over s = log2 m variables need to be s as well
-  size_t want = std::max(P->N, m), pw = 1;
-  while (pw < want) pw <<= 1;
-  size_t npw = 1;
-  while (npw < P->N) npw <<= 1;
-  if (pw != m || npw != m || lf_ajtai_width(aj) != P->N) {
-    delete P;
-    return LF_ERR_INVALID_ARG;  // CSError::InvalidSizeBounds / a witness of another width
-  }
-  P->c.resize((size_t)q * d);
-  P->S_off.resize(q + 1);
-  lf_ccs_get_structure(ccs, P->c.data(), P->S_off.data(), nullptr);
-  P->S_idx.resize(P->S_off[q]);
-  lf_ccs_get_structure(ccs, nullptr, nullptr, P->S_idx.data());
-  for (int i = 0; i < q; i++) {
-    bool zero = true;
-    for (int k = 0; k < d; k++) zero &= P->c[(size_t)i * d + k] == 0;
-    if (zero) continue;  // prepare_lin_sumcheck_polynomial skips c_i = 0 (linearization/utils.rs:71-84)
-    for (int k = P->S_off[i]; k < P->S_off[i + 1]; k++) P->lin_list.push_back(P->S_idx[k]);
-  }
-  P->nm_lin = (int)P->lin_list.size() + 1;
-  {
-    std::vector<int> pos_of(t, -1);
-    P->S_live.resize(P->S_idx.size());
-    for (size_t k = 0; k < P->S_idx.size(); k++) {
-      const int p = P->S_idx[k];
-      if (p < 0 || (size_t)p > P->lin_list.size()) {
-        // past the eq(beta) slot or negative: malformed, the reference would panic on the index
-        delete P;
-        lf_ctx_set_error(ctx, "lf_prover_create: a multiset index is negative or past the Mz MLE list and its "
-                              "eq(beta) slot");
-        return LF_ERR_INVALID_ARG;
-      }
-      if ((size_t)p == P->lin_list.size()) {
-        P->bad_S = true;
-        P->S_live[k] = 0;
-        continue;
-      }
-      const int j = P->lin_list[p];
-      if (pos_of[j] < 0) {
-        pos_of[j] = (int)P->mz_order.size();
-        P->mz_order.push_back(j);
-      }
-      P->S_live[k] = pos_of[j];
-    }
-    P->nlive = (int)P->mz_order.size();
-    for (int j = 0; j < t; j++)
-      if (pos_of[j] < 0) P->mz_order.push_back(j);
-  }
-  if (P->bad_S) {
-    // The reference's list position lin_list.size() is the eq(beta) MLE itself
-    // (linearization/utils.rs:71-84): a multiset naming it would put a second eq
-    // factor into its term, which the split-eq sumcheck (eq(beta) taken out of every
-    // term) does not express. Rejected here, by name, rather than mid-fold.
-    delete P;
-    lf_ctx_set_error(ctx, "lf_prover_create: a multiset index is the position of eq(beta) in the MLE list; "
-                          "multisets over eq(beta) are not supported");
-    return LF_ERR_UNSUPPORTED_CCS;
-  }
-  if (!P->bad_S) {
-    const size_t half = m / 2;
-    std::vector<uint8_t> row(m);
-    std::vector<std::vector<uint8_t>> pair(P->nlive, std::vector<uint8_t>(half));
-    for (int i = 0; i < P->nlive; i++) {
-      lf_ccs_row_live(ccs, P->mz_order[i], row.data());
-      for (size_t b = 0; b < half; b++) pair[i][b] = row[2 * b] | row[2 * b + 1];
-    }
-    P->act_off.assign(q + 1, 0);
-    for (int i = 0; i < q; i++) {
-      bool zero = true;  // c_i = 0: no active point
-      for (int k = 0; k < d; k++) zero &= P->c[(size_t)i * d + k] == 0;
-      if (!zero)
-        for (size_t b = 0; b < half; b++) {
-          bool on = true;
-          for (int k = P->S_off[i]; k < P->S_off[i + 1] && on; k++) on = pair[P->S_live[k]][b];
-          if (on) P->act_host.push_back((uint32_t)b);
-        }
-      P->act_off[i + 1] = (uint32_t)P->act_host.size();
-    }
-  }
-  P->nm_fold = 5 + 2 * P->K * P->tau;
-  // device memory, carved from one allocation
-  const size_t K = P->K, N = P->N, W = P->W, nn = P->nn, kd = P->kappa * d, tau = P->tau;
-  struct Part {
-    uint64_t **p;
-    size_t elems;
-  };
-  std::vector<Part> parts = {
-      {&P->z, n * d}, {&P->mz, (size_t)t * nn * d}, {&P->lin, (size_t)std::max(P->nlive, 1) * std::max<size_t>(nn / 4, 1) * d},
-      {&P->pt, (size_t)P->s * d}, {&P->beta, (size_t)P->s * d}, {&P->val, (size_t)(t + 3) * d},
-      {&P->fkc[0], K * N * d}, {&P->fkc[1], K * N * d}, {&P->fk[0], K * N * d}, {&P->fk[1], K * N * d},
-      {&P->wk[0], K * W * d}, {&P->wk[1], K * W * d}, {&P->y[0], K * kd}, {&P->y[1], K * kd},
-      {&P->cmd[0], kd}, {&P->cmd[1], kd}, {&P->xw[0], (l + 1) * d}, {&P->xw[1], (l + 1) * d},
-      {&P->xs, 2 * K * (l + 1) * d}, {&P->zdec[0], K * n * d}, {&P->zdec[1], K * n * d},
-      {&P->vs, 2 * K * tau * d}, {&P->us, 2 * K * t * d}, {&P->fold, (size_t)P->nm_fold * nn * d},
-      {&P->coef[0], K * tau * d}, {&P->coef[1], K * tau * d}, {&P->zeta, 2 * K * d}, {&P->mu, 2 * K * d},
-      {&P->theta, 2 * K * tau * d}, {&P->eta, 2 * K * t * d}, {&P->rho, 2 * K * d}, {&P->rhoc, 2 * K * d},
-      {&P->cm0, kd}, {&P->u0, (size_t)t * d}, {&P->x0, (l + 1) * d}, {&P->v0, tau * d}, {&P->r0, (size_t)P->s * d},
-      {&P->eq0, nn * d}, {&P->mzw, lf_ccs_weights_len(ccs)}, {&P->lev, (size_t)t * d},
-      {&P->chk, 2}, {reinterpret_cast<uint64_t **>(&P->act), (P->act_host.size() + 1) / 2}};
-  size_t total = 0;
-  for (auto &x : parts) total += (x.elems + 31) / 32 * 32;  // 256-B aligned parts
-  int prev = -1;
-  if (hipGetDevice(&prev) == hipSuccess && prev != P->device) (void)hipSetDevice(P->device);
-  hipError_t e = hipMalloc(&P->mem, total * 8);
-  if (prev >= 0 && prev != P->device) (void)hipSetDevice(prev);
-  if (e != hipSuccess) {
-    P->mem = nullptr;
-    delete P;
-    return e == hipErrorOutOfMemory ? LF_ERR_OUT_OF_MEMORY : LF_ERR_DEVICE;
-  }
-  size_t off = 0;
-  for (auto &x : parts) {
-    *x.p = P->mem + off;
-    off += (x.elems + 31) / 32 * 32;
-  }
-  if (!P->act_host.empty()) {
-    if (hipGetDevice(&prev) == hipSuccess && prev != P->device) (void)hipSetDevice(P->device);
-    e = hipMemcpy(P->act, P->act_host.data(), P->act_host.size() * 4, hipMemcpyHostToDevice);
-    if (prev >= 0 && prev != P->device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) {
-      delete P;
-      return LF_ERR_DEVICE;
-    }
-    P->act_host = std::vector<uint32_t>();
-  }
-  std::vector<Part> pins = {
-      {&P->hx[0], K * (l + 1) * d}, {&P->hx[1], K * (l + 1) * d}, {&P->hy[0], K * kd}, {&P->hy[1], K * kd},
-      {&P->hu[0], K * t * d}, {&P->hu[1], K * t * d}, {&P->hv[0], K * tau * d}, {&P->hv[1], K * tau * d},
-      {&P->hr[0], (size_t)P->s * d}, {&P->hr[1], (size_t)P->s * d}, {&P->htheta, 2 * K * tau * d},
-      {&P->heta, 2 * K * t * d}};
-  size_t ptotal = 0;
-  for (auto &x : pins) ptotal += (x.elems + 7) / 8 * 8;
-  if (hipGetDevice(&prev) == hipSuccess && prev != P->device) (void)hipSetDevice(P->device);
-  e = hipHostMalloc(reinterpret_cast<void **>(&P->pin), ptotal * 8, hipHostMallocDefault);
-  for (auto &ev : P->ev)
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-  if (prev >= 0 && prev != P->device) (void)hipSetDevice(prev);
-  if (e != hipSuccess) {
-    delete P;
-    return e == hipErrorOutOfMemory ? LF_ERR_OUT_OF_MEMORY : LF_ERR_DEVICE;
-  }
-  off = 0;
-  for (auto &x : pins) {
-    *x.p = P->pin + off;
-    off += (x.elems + 7) / 8 * 8;
-  }
-  *out = P;
+  LF_TRY(prover_shape(P.get()));
+  linearization_mle_list(P.get());
+  LF_TRY(live_matrix_order(P.get()));
+  active_points(P.get());
+  LF_TRY(prover_alloc(P.get()));
+  *out = P.release();
   return LF_OK;
 }
 
@@ -502,22 +921,16 @@ void lf_prover_destroy(lf_prover *P) { delete P; }
 
 int lf_linearize(lf_prover *P, const uint64_t *cm, const uint64_t *x_ccs, const lf_witness *w, lf_lcccs_mut *out,
                  uint64_t *lin_sumcheck, int repr) {
-  if (!P || !cm || (!x_ccs && P->l) || !w || !w->w_ccs || !w->f_coeff || !out || !lin_sumcheck || !out->r || !out->v ||
-      !out->cm || !out->u || (P->l && !out->x_w) || !out->h)
+  if (!P || !cm || (!x_ccs && P->l) || !w || !witness_ok(w, false, true) || !out || !lin_sumcheck ||
+      !lcccs_out_ok(P, out))
     return LF_ERR_INVALID_ARG;
-  if (repr != LF_REPR_CANONICAL && repr != LF_REPR_MONTGOMERY) return bad(P, LF_ERR_INVALID_ARG, "repr");
-  const int d = P->d, s = P->s, tau = P->tau, t = P->t;
+  if (!repr_ok(repr)) return bad(P, LF_ERR_INVALID_ARG, "repr");
+  const int d = P->d;
   const size_t l = P->l, kd = P->kappa * d;
-  std::vector<uint64_t> cmv(cm, cm + kd), xc(x_ccs ? x_ccs : cm, x_ccs ? x_ccs + l * d : cm);
-  if (repr == LF_REPR_MONTGOMERY) {
-    for (auto &x : cmv) x = gl::from_mont(x);
-    for (auto &x : xc) x = gl::from_mont(x);
-  }
+  const std::vector<uint64_t> cmv = canon(cm, kd, repr), xc = canon(x_ccs, l * d, repr);
+  DevGuard dg(P->device);
   Run R{P, lf_transcript_new(), (hipStream_t)lf_ctx_get_stream(P->ctx)};
-  struct TGuard {
-    lf_transcript *t;
-    ~TGuard() { lf_transcript_free(t); }
-  } tg{R.T};
+  TGuard tg{R.T};
   std::vector<uint64_t> r_lin, lv, lu;
   if (linearize_prepare(P, R, xc, w) || linearize(P, R, w, lin_sumcheck, r_lin, lv, lu)) return R.rc;
   // the LCCCS {r, v, cm, u, x_w = x_ccs, h = ONE} (linearization.rs:185-193)
@@ -526,18 +939,10 @@ int lf_linearize(lf_prover *P, const uint64_t *cm, const uint64_t *x_ccs, const 
   memcpy(out->cm, cmv.data(), kd * 8);
   memcpy(out->u, lu.data(), lu.size() * 8);
   if (l) memcpy(out->x_w, xc.data(), l * d * 8);
-  for (int i = 0; i < d; i++) out->h[i] = i % P->tb == 0 ? 1 : 0;
+  memcpy(out->h, P->one.data(), d * 8);
   if (repr == LF_REPR_MONTGOMERY) {
-    auto mont = [](uint64_t *p, size_t elems) {
-      for (size_t i = 0; i < elems; i++) p[i] = gl::to_mont(p[i]);
-    };
-    mont(out->r, (size_t)s * d);
-    mont(out->v, (size_t)tau * d);
-    mont(out->cm, kd);
-    mont(out->u, (size_t)t * d);
-    mont(out->x_w, l * d);
-    mont(out->h, d);
-    mont(lin_sumcheck, (size_t)s * (P->degree + 2) * d);
+    lcccs_to_mont(P, out);
+    to_mont(lin_sumcheck, (size_t)P->s * (P->degree + 2) * d);
   }
   return LF_OK;
 }
@@ -556,359 +961,61 @@ int lf_fold_prove(lf_prover *P, const lf_lcccs *acc, const lf_witness *w_acc, co
                   const uint64_t *x_ccs, const lf_witness *w_i, lf_lcccs_mut *out, const lf_witness *w_out,
                   lf_lfproof_mut *proof, int repr) {
   if (!P || !acc || !w_acc || !cm_i || (!x_ccs && P->l) || !w_i || !out || !w_out || !proof) return LF_ERR_INVALID_ARG;
-  if (repr != LF_REPR_CANONICAL && repr != LF_REPR_MONTGOMERY) return bad(P, LF_ERR_INVALID_ARG, "repr");
-  const int d = P->d, tb = P->tb, tau = P->tau, s = P->s, K = P->K, t = P->t;
-  const size_t N = P->N, W = P->W, n = P->n, nn = P->nn, l = P->l, kappa = P->kappa, kd = kappa * d;
-  const size_t ND = N * d;
-  if (acc->d != d || acc->r.n != (size_t)s || acc->v.n != (size_t)tau || acc->cm.n != kappa || acc->u.n != (size_t)t ||
-      acc->x_w.n != l || !acc->h)
+  if (!repr_ok(repr)) return bad(P, LF_ERR_INVALID_ARG, "repr");
+  const size_t d = P->d, s = P->s, tau = P->tau, K = P->K, t = P->t, l = P->l, kd = P->kappa * d;
+  if (!lcccs_sizes_ok(P, acc))
     return bad(P, LF_ERR_INCORRECT_LENGTH, "accumulator LCCCS sizes (r: s, v: tau, cm: kappa, u: t, x_w: l)");
-  if (!w_acc->f_coeff || !w_i->f_coeff || !w_i->w_ccs || !w_out->f || !w_out->f_coeff || !w_out->w_ccs)
+  if (!witness_ok(w_acc, false, false) || !witness_ok(w_i, false, true) || !witness_ok(w_out, true, true))
     return bad(P, LF_ERR_INVALID_ARG, "missing witness buffer");
   if (!proof->lin_sumcheck || !proof->lin_v || !proof->lin_u || !proof->fold_sumcheck || !proof->theta_s ||
-      !proof->eta_s || !out->r || !out->v || !out->cm || !out->u || (l && !out->x_w) || !out->h)
+      !proof->eta_s || !lcccs_out_ok(P, out))
     return bad(P, LF_ERR_INVALID_ARG, "missing output buffer");
   for (int side = 0; side < 2; side++)
     if (!proof->u_s[side] || !proof->v_s[side] || !proof->x_s[side] || !proof->y_s[side])
       return bad(P, LF_ERR_INVALID_ARG, "missing decomposition proof buffer");
-  // host copies of the public inputs in canonical form
-  auto canon = [&](const uint64_t *src, size_t elems) {
-    std::vector<uint64_t> v(src, src + elems);
-    if (repr == LF_REPR_MONTGOMERY)
-      for (auto &x : v) x = gl::from_mont(x);
-    return v;
-  };
-  const std::vector<uint64_t> ar = canon(acc->r.elems, (size_t)s * d), av = canon(acc->v.elems, (size_t)tau * d),
-                              acm = canon(acc->cm.elems, kd), au = canon(acc->u.elems, (size_t)t * d),
-                              axw = canon(acc->x_w.elems, l * d), ah = canon(acc->h, d), cmi = canon(cm_i, kd),
-                              xc = canon(x_ccs, l * d);
-  lf_ctx *C = P->ctx;
-  Run R{P, lf_transcript_new(), (hipStream_t)lf_ctx_get_stream(C)};
-  struct TGuard {
-    lf_transcript *t;
-    ~TGuard() { lf_transcript_free(t); }
-  } tg{R.T};
+  Run R{P, lf_transcript_new(), (hipStream_t)lf_ctx_get_stream(P->ctx)};
+  TGuard tg{R.T};
   lf_transcript_record(R.T);
   P->samples.clear();
-  int prev = -1;
-  if (hipGetDevice(&prev) == hipSuccess && prev != P->device) (void)hipSetDevice(P->device);
-  struct DGuard {
-    int prev, dev;
-    ~DGuard() {
-      if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-    }
-  } dg{prev, P->device};
-  std::vector<uint64_t> one(d, 0);
-  for (int i = 0; i < d; i += tb) one[i] = 1;
-
-  // the linearization's Mz MLEs need no challenge: on the device while the host absorbs
-  if (linearize_prepare(P, R, xc, w_i)) return R.rc;
-  // ---- absorb_public_input (zk_latticefold.rs:162-184)
-  R.absorb_label("acc");
-  R.absorb(ar.data(), s);
-  R.absorb(av.data(), tau);
-  R.absorb(acm.data(), kappa);
-  R.absorb(au.data(), t);
-  R.absorb(axw.data(), l);
-  R.absorb(ah.data(), 1);
-  R.absorb_label("cm_i");
-  R.absorb(cmi.data(), kappa);
-  R.absorb(xc.data(), l);
-
-  R.mark(LF_SPAN_PUBLIC_INPUT, false);
-  // ---- linearization (linearization.rs:153-197)
-  std::vector<uint64_t> r_lin, lv, lu;
-  if (linearize(P, R, w_i, proof->lin_sumcheck, r_lin, lv, lu)) return R.rc;
-  R.mark(LF_SPAN_LINEARIZATION);
-  // the linearized instance: {r, v, cm_i, u, x_ccs, h = ONE}
-
-  // ---- the two decompositions (decomposition.rs:33-88), device work of both first
-  R.h2d(P->cmd[0], acm.data(), kd);
-  R.h2d(P->cmd[1], cmi.data(), kd);
-  R.h2d(P->xw[0], axw.data(), l * d);  // x_w || h of each side
-  R.h2d(P->xw[0] + l * d, ah.data(), d);
-  R.h2d(P->xw[1], xc.data(), l * d);
-  R.h2d(P->xw[1] + l * d, one.data(), d);
-  for (int side = 0; side < 2; side++)
-    R.check(lf_dev_compute_x_s(C, &P->pr, P->xw[side], l + 1, P->xs + (size_t)side * K * (l + 1) * d), "compute_x_s");
-  lf_fold_step_bufs b{};
-  b.acc_f_coeff = w_acc->f_coeff;
-  b.f_coeff = const_cast<uint64_t *>(w_i->f_coeff);
-  b.acc_cm = P->cmd[0];
-  b.cm = P->cmd[1];
-  for (int side = 0; side < 2; side++) {
-    b.fk_coeff[side] = P->fkc[side];
-    b.fk[side] = P->fk[side];
-    b.wk[side] = P->wk[side];
-    b.y[side] = P->y[side];
+  DevGuard dg(P->device);
+  Fold F{w_acc, w_i, w_out, out, proof};
+  F.ar = canon(acc->r.elems, s * d, repr);
+  F.av = canon(acc->v.elems, tau * d, repr);
+  F.acm = canon(acc->cm.elems, kd, repr);
+  F.au = canon(acc->u.elems, t * d, repr);
+  F.axw = canon(acc->x_w.elems, l * d, repr);
+  F.ah = canon(acc->h, d, repr);
+  F.cmi = canon(cm_i, kd, repr);
+  F.xc = canon(x_ccs, l * d, repr);
+  F.M = P->fold;
+  F.mstride = P->nn * d;
+  F.ng = (P->K + MZ_GROUP - 1) / MZ_GROUP;
+  F.digits = P->pr.b_small == 2;
+  for (const auto &ph : FOLD_PHASES) {
+    if (const int rc = ph.run(P, R, F)) return rc;
+    R.mark(ph.span, ph.sync);
   }
-  if (R.rc == LF_OK) R.check(lf_dev_decompose_commit(C, P->aj, &P->pr, W, &b), "decompose + commit_witnesses");
-  // z_k = x_s[k] || w_ccs_k (compute_mz_mles, :229-256) for the u_s (and later eta_s), one
-  // launch per side (the stream's queue holds a bounded number of commands: every one
-  // saved is host time the transcript gets back)
-  for (int side = 0; side < 2; side++)
-    R.hip(lfk::assemble_z(P->xs + (size_t)side * K * (l + 1) * d, P->wk[side], K, l + 1, W, d, P->zdec[side], R.st),
-          "z_k");
-  // per side: v_s, u_s at the side's point, then its messages back to pinned memory
-  // behind events, so the host absorbs while the device evaluates: x_s, y_s and v_s
-  // of a side first, then u_s in groups of MZ_GROUP instances (one event each: the
-  // host starts on instance 0 as soon as its u_s is back), and the challenge-
-  // independent folding MLEs (the f_hat MLEs of the 2K decomposed witnesses, eq(r_i);
-  // create_sumcheck_polynomial, folding/utils.rs:196-255) behind them
-  uint64_t *M = P->fold;
-  const size_t mstride = nn * d;
-  // eq(r_i) of each side is the folding prover's eq(r_i) MLE (M slots 0 and 2; the
-  // linearization left eq(r_lin) in slot 2): v_s and u_s read it from there
-  R.h2p2d(P->pt, P->hr[0], ar.data(), (size_t)s * d);
-  R.check(lf_dev_eq_table(C, d, P->pt, s, M), "eq(r_0)");
-  const int G = MZ_GROUP, ng = (K + G - 1) / G;
-  // The u_s groups go to the device from a second host thread (its own Run, so the
-  // error state is not shared): with the stream's queue deep, every enqueue blocks the
-  // calling thread for tens of microseconds, which the transcript thread would
-  // otherwise spend before and between its absorbs. `posted` counts the groups whose
-  // event is recorded; the absorb loop waits on a group's event only after that.
-  const bool digits = P->pr.b_small == 2;  // f_hat values in {-1, 0, 1}: read from the coefficient rows
-  std::atomic<int> posted{0};
-  Run RE = R;
-  std::string err_enq;  // the enqueue thread's own error text, merged into P->err after the join
-  RE.err = &err_enq;
-  auto enqueue_side = [&](Run &Q, int side) {
-    const uint64_t *eq_s = M + (size_t)(2 * side) * mstride;
-    Q.check(lf_dev_fhat_evaluate_eq(C, d, P->fkc[side], N, ND, K, s, eq_s, P->vs + (size_t)side * K * tau * d), "v_s");
-    Q.d2p(P->hx[side], P->xs + (size_t)side * K * (l + 1) * d, (size_t)K * (l + 1) * d);
-    Q.d2p(P->hy[side], P->y[side], (size_t)K * kd);
-    Q.d2p(P->hv[side], P->vs + (size_t)side * K * tau * d, (size_t)K * tau * d);
-    Q.check(lf_dev_mz_weights(C, P->ccs, s, eq_s, P->mzw), "u_s weights");
-    for (int g = 0; g < ng; g++) {
-      const int k0 = g * G, nk = std::min(G, K - k0);
-      uint64_t *us = P->us + ((size_t)side * K + k0) * t * d;
-      Q.check(lf_dev_mz_dots(C, P->ccs, P->mzw, P->zdec[side] + (size_t)k0 * n * d, nk, us), "u_s");
-      Q.d2p(P->hu[side] + (size_t)k0 * t * d, us, (size_t)nk * t * d);
-      Q.hip(hipEventRecord(P->ev[2 + side * ng + g], Q.st), "event");
-      posted.store(side * ng + g + 1, std::memory_order_release);
-    }
-  };
-  auto enqueue_all = [&] {
-    (void)hipSetDevice(P->device);
-    if (RE.rc == LF_OK) {
-      enqueue_side(RE, 0);
-      enqueue_side(RE, 1);
-      if (!digits)
-        for (int sd = 0; sd < 2; sd++)
-          RE.hip(lfk::get_fhat(P->fkc[sd], N, d, s, M + (5 + (size_t)sd * K * tau) * mstride, RE.st, K, ND), "f_hat");
-    }
-    posted.store(1 << 30, std::memory_order_release);  // done (also on an error)
-  };
-  std::thread enq;
-  try {
-    enq = std::thread(enqueue_all);
-  } catch (const std::exception &) {  // no thread to be had: enqueue everything here first
-    enqueue_all();
-  }
-  auto join = [&] {
-    if (enq.joinable()) enq.join();
-    if (RE.rc != LF_OK && R.rc == LF_OK) {
-      R.rc = RE.rc;
-      P->err = err_enq;
-    }
-    return R.rc;
-  };
-  R.mark(LF_SPAN_DECOMPOSITION, false);
-  for (int side = 0; side < 2; side++)
-    for (int k = 0; k < K; k++) {  // the decomposed instances' messages (:58-64)
-      if (k % G == 0) {
-        const int g = side * ng + k / G;
-        while (posted.load(std::memory_order_acquire) <= g) std::this_thread::yield();
-        if (posted.load(std::memory_order_acquire) >= (1 << 30) && RE.rc != LF_OK) return join();
-        if (R.wait(P->ev[2 + g])) return join();
-      }
-      const size_t ox = (size_t)k * (l + 1) * d, oy = (size_t)k * kd, ou = (size_t)k * t * d, ov = (size_t)k * tau * d;
-      memcpy(proof->x_s[side] + ox, P->hx[side] + ox, (l + 1) * d * 8);
-      memcpy(proof->y_s[side] + oy, P->hy[side] + oy, kd * 8);
-      memcpy(proof->u_s[side] + ou, P->hu[side] + ou, (size_t)t * d * 8);
-      memcpy(proof->v_s[side] + ov, P->hv[side] + ov, (size_t)tau * d * 8);
-      R.absorb(proof->x_s[side] + ox, l + 1);
-      R.absorb(proof->y_s[side] + oy, kappa);
-      R.absorb(proof->u_s[side] + ou, t);
-      R.absorb(proof->v_s[side] + ov, tau);
-    }
-  if (join()) return R.rc;
-  R.mark(LF_SPAN_DECOMPOSITION_TRANSCRIPT, false);
-  // ---- folding (folding.rs:42-130)
-  R.absorb_label("alpha_s");  // squeeze_alpha_beta_zeta_mu (folding/utils.rs:51-96)
-  const std::vector<uint64_t> alpha = R.challenges(2 * K);
-  R.absorb_label("zeta_s");
-  const std::vector<uint64_t> zeta = R.challenges(2 * K);
-  R.absorb_label("mu_s");
-  std::vector<uint64_t> mu = R.challenges(2 * K - 1);
-  mu.insert(mu.end(), one.begin(), one.end());
-  R.absorb_label("beta_s");
-  const std::vector<uint64_t> fbeta = R.challenges(s);
-  R.h2d(P->zeta, zeta.data(), 2 * (size_t)K * d);
-  R.h2d(P->mu, mu.data(), 2 * (size_t)K * d);
-  R.h2d(P->beta, fbeta.data(), (size_t)s * d);
-  // Horner weights alpha_k^(j+1) of each side's f_hat MLEs (prepare_g1_and_3_k_mles_list, :519-541)
-  for (int side = 0; side < 2; side++) {
-    std::vector<uint64_t> cf((size_t)K * tau * d);
-    for (int k = 0; k < K; k++) {
-      const uint64_t *a = alpha.data() + (size_t)(side * K + k) * d;  // broadcast: slot 0 holds the base value
-      uint64_t pw[3] = {a[0], tb == 3 ? a[1] : 0, tb == 3 ? a[2] : 0};
-      for (int j = 0; j < tau; j++) {
-        broadcast(pw, tb, d, cf.data() + ((size_t)k * tau + j) * d);
-        uint64_t nx[3];
-        gl::base_mul(pw, a, nx, tb);
-        memcpy(pw, nx, sizeof(pw));
-      }
-    }
-    R.h2d(P->coef[side], cf.data(), cf.size());
-  }
-  // the MLEs [eq(r_0), g1, eq(r_1), g3, eq(beta), f_hat (2K x tau)] (create_sumcheck_polynomial,
-  // :196-255): eq(r_i) were enqueued before the decomposition transcript; the f_hat MLEs
-  // (Witness::get_fhat of the decomposed witnesses) are not materialised for B_SMALL = 2 --
-  // their values are the digits of the coefficient rows P->fkc, which g1 / g3 and the
-  // sumcheck's first round read directly (lf_sumcheck_prove_fold_digits)
-  // both sides' challenged Mz MLEs in one pass over the matrices (g1, g3 slots)
-  R.check(lf_dev_mz_challenged_pair(C, P->ccs, P->zdec[0], P->zeta, P->zdec[1], P->zeta + (size_t)K * d, K, s,
-                                    M + mstride, M + 3 * mstride),
-          "challenged Mz");
-  for (int side = 0; side < 2; side++) {
-    uint64_t *g = M + (size_t)(2 * side + 1) * mstride;
-    if (digits)
-      R.hip(lfk::fhat_lincomb_digits(P->fkc[side], K, N, ND, P->coef[side], s, d, g, R.st), "g");
-    else
-      R.check(lf_dev_mle_lincomb(C, d, M + (5 + (size_t)side * K * tau) * mstride, mstride, K * tau, s, P->coef[side], g),
-              "g");
-  }
-  R.check(lf_dev_eq_table(C, d, P->beta, s, M + 4 * mstride), "eq(beta)");
-  std::vector<uint64_t> rnd((size_t)s * tb);
-  R.mark(LF_SPAN_FOLDING_MLES);
-  {
-    lf_comb cb{};
-    cb.kind = LF_COMB_FOLDING;
-    cb.nk = 2 * K;
-    cb.tau = tau;
-    cb.bsmall = (int)P->pr.b_small;
-    cb.mu = P->mu;
-    if (R.rc == LF_OK)
-      R.check(digits
-                  ? lf_sumcheck_prove_fold_digits(C, R.T, &cb, M, P->fkc[0], P->fkc[1], K, N, ND, s, d, M + 5 * mstride,
-                                                  proof->fold_sumcheck, rnd.data())
-                  : lf_sumcheck_prove(C, R.T, &cb, M, P->nm_fold, s, d, 2 * cb.bsmall, proof->fold_sumcheck, rnd.data()),
-              "folding sumcheck");
-  }
-  if (R.rc) return R.rc;
-  R.mark(LF_SPAN_FOLDING_SUMCHECK);
-  std::vector<uint64_t> r0((size_t)s * d);
-  for (int i = 0; i < s; i++) broadcast(rnd.data() + (size_t)i * tb, tb, d, r0.data() + (size_t)i * d);
-  R.h2d(P->r0, r0.data(), (size_t)s * d);
-  // theta_s = f_hat(w_i)(r_0), eta_s = MLE(M_j z_i)(r_0) (get_thetas / get_etas, :236-256):
-  // theta_s and side 0's eta_s come back first, so the host absorbs them while the
-  // device evaluates side 1's eta_s
-  // one eq(r_0) table and one set of Mz weights at r_0 for both sides
-  R.check(lf_dev_eq_table(C, d, P->r0, s, P->eq0), "eq(r_0)");
-  for (int side = 0; side < 2; side++)
-    R.check(lf_dev_fhat_evaluate_eq(C, d, P->fkc[side], N, ND, K, s, P->eq0, P->theta + (size_t)side * K * tau * d),
-            "theta");
-  R.d2p(P->htheta, P->theta, 2 * (size_t)K * tau * d);
-  R.hip(hipEventRecord(P->ev[0], R.st), "event");
-  R.check(lf_dev_mz_weights(C, P->ccs, s, P->eq0, P->mzw), "eta weights");
-  if (R.rc) return R.rc;
-  // the eta_s groups of both sides from a second host thread, as the u_s groups above
-  std::atomic<int> eposted{0};
-  Run RQ = R;
-  std::thread eenq([&] {
-    (void)hipSetDevice(P->device);
-    for (int side = 0; side < 2 && RQ.rc == LF_OK; side++)
-      for (int gg = 0; gg < ng; gg++) {  // instance groups in absorb order
-        const int g = side * ng + gg, k0 = gg * G, nk = std::min(G, K - k0);
-        const size_t o = ((size_t)side * K + k0) * t * d;
-        RQ.check(lf_dev_mz_dots(C, P->ccs, P->mzw, P->zdec[side] + (size_t)k0 * n * d, nk, P->eta + o), "eta");
-        RQ.d2p(P->heta + o, P->eta + o, (size_t)nk * t * d);
-        RQ.hip(hipEventRecord(P->ev[2 + g], RQ.st), "event");
-        eposted.store(g + 1, std::memory_order_release);
-      }
-    eposted.store(1 << 30, std::memory_order_release);
-  });
-  auto ejoin = [&] {
-    if (eenq.joinable()) eenq.join();
-    if (RQ.rc != LF_OK && R.rc == LF_OK) R.rc = RQ.rc;
-    return R.rc;
-  };
-  R.mark(LF_SPAN_EVALUATIONS, false);
-  if (R.wait(P->ev[0])) return ejoin();
-  memcpy(proof->theta_s, P->htheta, 2 * (size_t)K * tau * d * 8);
-  for (int i = 0; i < 2 * K; i++) R.absorb(proof->theta_s + (size_t)i * tau * d, tau);
-  for (int side = 0; side < 2; side++)
-    for (int k = 0; k < K; k++) {
-      if (k % G == 0) {
-        const int g = side * ng + k / G;
-        while (eposted.load(std::memory_order_acquire) <= g) std::this_thread::yield();
-        if (eposted.load(std::memory_order_acquire) >= (1 << 30) && RQ.rc != LF_OK) return ejoin();
-        if (R.wait(P->ev[2 + g])) return ejoin();
-      }
-      const size_t o = ((size_t)side * K + k) * t * d;
-      memcpy(proof->eta_s + o, P->heta + o, (size_t)t * d * 8);
-      R.absorb(proof->eta_s + o, t);
-    }
-  if (ejoin()) return R.rc;
-  // get_rhos (folding/utils.rs:116-127): 2K - 1 short challenges and ONE, then CRT
-  R.absorb_label("rho_s");
-  std::vector<uint64_t> rc(2 * (size_t)K * d, 0);
-  if (lf_transcript_get_short_challenges(R.T, d, 2 * K - 1, rc.data()) != LF_OK)
-    return bad(P, LF_ERR_CHALLENGE_BYTES, "short challenges");
-  rc[(size_t)(2 * K - 1) * d] = 1;
-  R.mark(LF_SPAN_FOLDING_TRANSCRIPT);
-  R.h2d(P->rhoc, rc.data(), rc.size());
-  R.d2d(P->rho, P->rhoc, rc.size());
-  R.check(lf_dev_crt(C, P->rho, 2 * K, d), "CRT(rho)");
-  // f_0, cm_0, Witness::from_f(f_0) (:112-122), then v_0, u_0, x_0 (compute_v0_u0_x0_cm_0, :456-517)
-  b.rho = P->rho;
-  b.f0 = w_out->f;
-  b.f0_coeff = w_out->f_coeff;
-  b.w_ccs0 = w_out->w_ccs;
-  b.cm0 = P->cm0;
-  if (R.rc == LF_OK) R.check(lf_dev_fold_combine(C, P->aj, &P->pr, W, &b), "fold");
-  R.check(lf_dev_fold_lcccs(C, d, 2 * K, P->rho, P->rhoc, P->eta, t, P->xs, l + 1, P->theta, P->u0, P->x0, P->v0),
-          "v_0, u_0, x_0");
-  if (R.rc) return R.rc;
-  // prepare_public_output (folding.rs:381-392): x_w = x_0[..l], h = x_0[l]
-  std::vector<uint64_t> x0((l + 1) * d);
-  R.d2h(out->cm, P->cm0, kd);
-  R.d2h(out->u, P->u0, (size_t)t * d);
-  R.d2h(out->v, P->v0, (size_t)tau * d);
-  R.d2h(x0.data(), P->x0, (l + 1) * d);
-  R.check(lf_ctx_sync(C), "sync");
-  if (R.rc) return R.rc;
-  R.mark(LF_SPAN_FOLD);
   P->samples.resize(lf_transcript_samples(R.T, nullptr, 0));
   lf_transcript_samples(R.T, P->samples.data(), P->samples.size());
-  memcpy(out->r, r0.data(), r0.size() * 8);
-  if (l) memcpy(out->x_w, x0.data(), l * d * 8);
-  memcpy(out->h, x0.data() + l * d, d * 8);
-  memcpy(proof->lin_v, lv.data(), lv.size() * 8);
-  memcpy(proof->lin_u, lu.data(), lu.size() * 8);
+  memcpy(out->r, F.r0.data(), F.r0.size() * 8);
+  if (l) memcpy(out->x_w, F.x0.data(), l * d * 8);
+  memcpy(out->h, F.x0.data() + l * d, d * 8);
+  memcpy(proof->lin_v, F.lv.data(), F.lv.size() * 8);
+  memcpy(proof->lin_u, F.lu.data(), F.lu.size() * 8);
   if (repr == LF_REPR_MONTGOMERY) {
-    auto mont = [](uint64_t *p, size_t elems) {
-      for (size_t i = 0; i < elems; i++) p[i] = gl::to_mont(p[i]);
-    };
-    mont(out->r, (size_t)s * d);
-    mont(out->v, (size_t)tau * d);
-    mont(out->cm, kd);
-    mont(out->u, (size_t)t * d);
-    mont(out->x_w, l * d);
-    mont(out->h, d);
-    mont(proof->lin_sumcheck, (size_t)s * (P->degree + 2) * d);
-    mont(proof->lin_v, (size_t)tau * d);
-    mont(proof->lin_u, (size_t)t * d);
+    lcccs_to_mont(P, out);
+    to_mont(proof->lin_sumcheck, s * (P->degree + 2) * d);
+    to_mont(proof->lin_v, tau * d);
+    to_mont(proof->lin_u, t * d);
     for (int side = 0; side < 2; side++) {
-      mont(proof->u_s[side], (size_t)K * t * d);
-      mont(proof->v_s[side], (size_t)K * tau * d);
-      mont(proof->x_s[side], (size_t)K * (l + 1) * d);
-      mont(proof->y_s[side], (size_t)K * kd);
+      to_mont(proof->u_s[side], K * t * d);
+      to_mont(proof->v_s[side], K * tau * d);
+      to_mont(proof->x_s[side], K * (l + 1) * d);
+      to_mont(proof->y_s[side], K * kd);
     }
-    mont(proof->fold_sumcheck, (size_t)s * (2 * P->pr.b_small + 1) * d);
-    mont(proof->theta_s, 2 * (size_t)K * tau * d);
-    mont(proof->eta_s, 2 * (size_t)K * t * d);
+    to_mont(proof->fold_sumcheck, s * (2 * P->pr.b_small + 1) * d);
+    to_mont(proof->theta_s, 2 * K * tau * d);
+    to_mont(proof->eta_s, 2 * K * t * d);
   }
   return LF_OK;
 }
@@ -955,24 +1062,18 @@ int lf_lcccs_check(lf_prover *P, const lf_lcccs *acc, const lf_witness *w, uint6
                    int repr) {
   if (!P || !acc || !w || !failed) return LF_ERR_INVALID_ARG;
   *failed = LF_REL_OK;
-  if (repr != LF_REPR_CANONICAL && repr != LF_REPR_MONTGOMERY) return bad(P, LF_ERR_INVALID_ARG, "repr");
+  if (!repr_ok(repr)) return bad(P, LF_ERR_INVALID_ARG, "repr");
   const int d = P->d, tau = P->tau, s = P->s, t = P->t;
-  const size_t l = P->l, kd = P->kappa * d;
-  if (acc->d != d || acc->r.n != (size_t)s || acc->v.n != (size_t)tau || acc->cm.n != P->kappa || acc->u.n != (size_t)t ||
-      acc->x_w.n != l || !acc->h)
+  if (!lcccs_sizes_ok(P, acc))
     return bad(P, LF_ERR_INCORRECT_LENGTH, "LCCCS sizes (r: s, v: tau, cm: kappa, u: t, x_w: l)");
-  if (!w->f || !w->f_coeff || !w->w_ccs) return bad(P, LF_ERR_INVALID_ARG, "missing witness buffer");
-  auto canon = [&](const uint64_t *src, size_t elems) {
-    std::vector<uint64_t> v(src, src + elems);
-    if (repr == LF_REPR_MONTGOMERY)
-      for (auto &x : v) x = gl::from_mont(x);
-    return v;
-  };
-  const std::vector<uint64_t> ar = canon(acc->r.elems, (size_t)s * d), av = canon(acc->v.elems, (size_t)tau * d),
-                              acm = canon(acc->cm.elems, kd), au = canon(acc->u.elems, (size_t)t * d),
-                              axw = canon(acc->x_w.elems, l * d), ah = canon(acc->h, d);
+  if (!witness_ok(w, true, true)) return bad(P, LF_ERR_INVALID_ARG, "missing witness buffer");
+  const std::vector<uint64_t> ar = canon(acc->r.elems, (size_t)s * d, repr),
+                              av = canon(acc->v.elems, (size_t)tau * d, repr),
+                              acm = canon(acc->cm.elems, P->kappa * d, repr),
+                              au = canon(acc->u.elems, (size_t)t * d, repr),
+                              axw = canon(acc->x_w.elems, P->l * d, repr), ah = canon(acc->h, d, repr);
   lf_ctx *C = P->ctx;
-  OnDevice dg(P->device);
+  DevGuard dg(P->device);
   Run R{P, nullptr, (hipStream_t)lf_ctx_get_stream(C)};
   if (witness_checks(P, R, w, acm.data(), bound, norm, failed)) return R.rc;
   if (*failed) return LF_ERR_VERIFICATION;
@@ -996,24 +1097,16 @@ int lf_cccs_check(lf_prover *P, const uint64_t *cm, const uint64_t *x_ccs, const
   if (!P || !cm || (!x_ccs && P->l) || !w || !failed) return LF_ERR_INVALID_ARG;
   *failed = LF_REL_OK;
   if (row) *row = -1;
-  if (repr != LF_REPR_CANONICAL && repr != LF_REPR_MONTGOMERY) return bad(P, LF_ERR_INVALID_ARG, "repr");
-  if (!w->f || !w->f_coeff || !w->w_ccs) return bad(P, LF_ERR_INVALID_ARG, "missing witness buffer");
-  const int d = P->d;
-  const size_t l = P->l, kd = P->kappa * d;
-  std::vector<uint64_t> cmv(cm, cm + kd), xc(x_ccs ? x_ccs : cm, x_ccs ? x_ccs + l * d : cm);
-  if (repr == LF_REPR_MONTGOMERY) {
-    for (auto &x : cmv) x = gl::from_mont(x);
-    for (auto &x : xc) x = gl::from_mont(x);
-  }
+  if (!repr_ok(repr)) return bad(P, LF_ERR_INVALID_ARG, "repr");
+  if (!witness_ok(w, true, true)) return bad(P, LF_ERR_INVALID_ARG, "missing witness buffer");
+  const std::vector<uint64_t> cmv = canon(cm, P->kappa * P->d, repr), xc = canon(x_ccs, P->l * P->d, repr);
   lf_ctx *C = P->ctx;
-  OnDevice dg(P->device);
+  DevGuard dg(P->device);
   Run R{P, nullptr, (hipStream_t)lf_ctx_get_stream(C)};
   if (witness_checks(P, R, w, cmv.data(), bound, norm, failed)) return R.rc;
   if (*failed) return LF_ERR_VERIFICATION;
   // CCS::check_relation of z = x_ccs || 1 || w_ccs (arith.rs:78-105)
-  std::vector<uint64_t> one(d, 0);
-  for (int i = 0; i < d; i += P->tb) one[i] = 1;
-  assemble_z(P, R, xc.data(), one.data(), w);
+  assemble_z(P, R, xc.data(), P->one.data(), w);
   if (R.rc) return R.rc;
   int64_t fb = -1;
   const int rc = lf_dev_ccs_check_relation(C, P->ccs, P->z, 1, nullptr, &fb);

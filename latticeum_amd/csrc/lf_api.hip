@@ -348,8 +348,9 @@ int lf_ctx_create(int device, lf_ctx **out) {
   return LF_OK;
 }
 
-void lf_ctx_destroy(lf_ctx *c) {
-  if (!c) return;
+// also what a failed lf_ctx_create leaves behind
+lf_ctx::~lf_ctx() {
+  lf_ctx *c = this;
   DevGuard g(c);
   (void)hipStreamSynchronize(c->cur);
   // a batched contraction this context led on the caller's contract stream reads its buffers
@@ -387,8 +388,9 @@ void lf_ctx_destroy(lf_ctx *c) {
   if (c->d_err) (void)hipFree(c->d_err);
   if (c->d_sync) (void)hipFree(c->d_sync);
   if (c->own) (void)hipStreamDestroy(c->own);
-  delete c;
 }
+
+void lf_ctx_destroy(lf_ctx *c) { delete c; }
 
 const char *lf_ctx_last_error(const lf_ctx *c) { return c ? c->last_error.c_str() : ""; }
 void lf_ctx_set_error(lf_ctx *c, const char *msg) {

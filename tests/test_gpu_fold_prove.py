@@ -10,7 +10,7 @@ import latticeum_amd as LA
 import nifs as N
 import oracle as O
 
-LF_ERR_INVALID_ARG = 1  # lf.h
+LF_ERR_INVALID_ARG, LF_ERR_INCORRECT_LENGTH = 1, 7  # lf.h
 
 pytestmark = pytest.mark.gpu
 
@@ -33,14 +33,18 @@ def flat(xs):
     return np.concatenate([np.asarray(x, np.uint64).ravel() for x in xs]) if len(xs) else np.zeros(0, np.uint64)
 
 
-def setup(ctx, d, W, l, t, deg, kappa, seed, empty=0.0, scalar=False):
-    pr_o = N.Params(d)
+def setup(ctx, d, W, l, t, deg, kappa, seed, empty=0.0, scalar=False, b_small=None, K=None):
+    pr_o, pr = N.Params(d), LA.goldilocks_dp(d)
+    if b_small is not None:
+        pr_o.b_small = pr.b_small = b_small
+    if K is not None:
+        pr_o.K = pr.K = K
     ccs = N.satisfied_ccs(d, W, l, t, deg, seed, pr_o, empty=empty, scalar=scalar)
     Nn = W * pr_o.L
     A = O.fill_uniform(kappa * Nn * d, seed + 6)
     sch = LA.AjtaiCommitmentScheme(ctx, A.reshape(kappa, Nn, d))
     M = LA.CCSMatrices(ctx, d, ccs.m, ccs.n, ccs.mats)
-    prover = LA.Prover(ctx, sch, LA.goldilocks_dp(d), M, l, deg, np.concatenate(ccs.c), ccs.S)
+    prover = LA.Prover(ctx, sch, pr, M, l, deg, np.concatenate(ccs.c), ccs.S)
     return pr_o, ccs, A, prover
 
 
@@ -189,6 +193,138 @@ def test_fold_prove_empty_rows_matches_oracle(d, W, l, t, deg, kappa, scalar):
         w_out = {"w_ccs": zeros(W * d), "f": zeros(Nn * d), "f_coeff": zeros(Nn * d)}
         out, pf = prover.fold_prove(acc_dict(acc), dev_wit(Wa), cmi, flat(xi), dev_wit(Wi), w_out)
         check_against_oracle(out, pf, w_out, o_out, o_w0, o_proof)
+    finally:
+        ctx.close()
+
+
+class Case:
+    """one satisfied CCS, an accumulator and a fresh instance for it, and the oracle's fold() of the two"""
+
+    def __init__(self, ctx, d, W, l, t, deg, kappa, seed=7, **params):
+        self.shape = (d, W, l, t, deg, kappa)
+        self.pr_o, self.ccs, self.A, self.prover = setup(ctx, d, W, l, t, deg, kappa, seed, **params)
+        self.xa, self.Wa = witness(self.ccs, self.pr_o, seed + 4)
+        self.xi, self.Wi = witness(self.ccs, self.pr_o, seed + 5)
+        self.Nn = W * self.pr_o.L
+        cma = O.ajtai_commit(self.A, kappa, self.Nn, d, self.Wa.f)
+        self.cmi = O.ajtai_commit(self.A, kappa, self.Nn, d, self.Wi.f)
+        self.acc = N.linearize_fresh(self.ccs, cma, self.xa, self.Wa, self.pr_o)
+        self.oracle = N.fold_prove(self.ccs, self.A, kappa, self.acc, self.Wa, self.cmi, self.xi, self.Wi, self.pr_o)
+
+    def w_out(self):
+        d, W = self.shape[:2]
+        return {"w_ccs": zeros(W * d), "f": zeros(self.Nn * d), "f_coeff": zeros(self.Nn * d)}
+
+    def fold(self, **kw):
+        w_out = self.w_out()
+        return self.prover.fold_prove(acc_dict(self.acc), dev_wit(self.Wa), self.cmi, flat(self.xi), dev_wit(self.Wi),
+                                      w_out, **kw) + (w_out,)
+
+    def check(self, out, pf, w_out):
+        """the oracle's fold() bit for bit, and the restated verifier accepts the device's proof"""
+        d, _, l, _, _, kappa = self.shape
+        check_against_oracle(out, pf, w_out, *self.oracle)
+        tau = N.tb(d) if d == 24 else 1
+        v = N.fold_verify(self.ccs, self.acc, self.cmi, self.xi,
+                          proof_from_device(pf, d, self.pr_o.K, tau, self.ccs.t, l, kappa), self.pr_o)
+        assert np.array_equal(flat(v.r), out["r"]) and np.array_equal(v.cm, out["cm"])
+
+
+@pytest.mark.parametrize("d,W,l,t,deg,kappa", [(24, 5, 2, 4, 2, 3), (16, 5, 2, 4, 2, 3)])
+def test_fold_prove_b_small_4_matches_oracle(d, W, l, t, deg, kappa):
+    """B_SMALL = 4, K = 8: the f_hat MLEs are materialised (get_fhat behind the u_s groups,
+    lf_dev_mle_lincomb for g1 / g3, lf_sumcheck_prove over all nm_fold MLEs) instead of
+    read as digits from the coefficient rows"""
+    ctx = LA.Context(0)
+    try:
+        case = Case(ctx, d, W, l, t, deg, kappa, b_small=4, K=8)
+        case.check(*case.fold())
+    finally:
+        ctx.close()
+
+
+@pytest.mark.parametrize("d,W,l,t,deg,kappa", [(24, 5, 0, 4, 2, 3), (16, 7, 0, 5, 3, 3)])
+def test_fold_prove_no_public_input_matches_oracle(d, W, l, t, deg, kappa):
+    """l = 0: z = 1 || w_ccs, no x_ccs, x_w empty on both sides"""
+    ctx = LA.Context(0)
+    try:
+        case = Case(ctx, d, W, l, t, deg, kappa)
+        out, pf, w_out = case.fold()
+        case.check(out, pf, w_out)
+        assert out["x_w"].size == 0
+    finally:
+        ctx.close()
+
+
+def test_fold_prove_phase_spans():
+    """Prover.timing: every fold() phase reports its span, the spans fit into the call's
+    wall time, and timing changes nothing the call computes"""
+    import time
+    ctx = LA.Context(0)
+    try:
+        case = Case(ctx, 24, 5, 2, 4, 2, 3)
+        out, pf, vv, w_out = case.fold(vars=True)
+        case.prover.timing(True)
+        t0 = time.perf_counter()
+        out_t, pf_t, vv_t, w_out_t = case.fold(vars=True)
+        wall_ms = (time.perf_counter() - t0) * 1e3
+        spans = case.prover.timing(False)
+        assert set(spans) == set(LA.Prover.SPANS)
+        assert all(spans[k] > 0 for k in LA.Prover.SPANS), spans
+        assert sum(spans.values()) <= wall_ms, (spans, wall_ms)
+        for k in out:
+            assert np.array_equal(out_t[k], out[k]), k
+        for k in pf:
+            assert np.array_equal(flat(pf_t[k]), flat(pf[k])), k
+        for k in vv:
+            assert np.array_equal(vv_t[k], vv[k]), k
+        for k in w_out:
+            assert np.array_equal(host(w_out_t[k]), host(w_out[k])), k
+        assert not any(case.prover.timing(False).values())
+    finally:
+        ctx.close()
+
+
+def test_fold_prove_argument_errors():
+    """lf_fold_prove's own argument checks, through the C ABI: each names what is wrong
+    in lf_prover_last_error and returns before any launch, and the prover folds
+    correctly afterwards"""
+    from latticeum_amd._lib import C, LfLfproofMut, LfWitness
+    ctx = LA.Context(0)
+    try:
+        case = Case(ctx, 24, 5, 2, 4, 2, 3)
+        P, d = case.prover, 24
+        pf_bytes = max(P.s * (P.degree + 2), P.s * (2 * P.pr.b_small + 1), 2 * P.pr.K * max(P.t, P.kappa)) * d * 8
+        buf = C.create_string_buffer(pf_bytes)  # every proof field may point here: no call below gets to write
+        wa, wi, wo = dev_wit(case.Wa), dev_wit(case.Wi), case.w_out()
+
+        def call(acc=None, null_f_out=False, null_y1=False):
+            A, keep = P._lcccs_in(acc if acc is not None else acc_dict(case.acc))
+            out, O_ = P._lcccs_out()
+            PM = LfLfproofMut()
+            for k, _ in LfLfproofMut._fields_:
+                if k in ("u_s", "v_s", "x_s", "y_s"):
+                    getattr(PM, k)[0] = getattr(PM, k)[1] = C.addressof(buf)
+                else:
+                    setattr(PM, k, C.addressof(buf))
+            if null_y1:
+                PM.y_s[1] = None
+            a, i, o = P._witness(wa), P._witness(wi), P._witness(wo)
+            if null_f_out:
+                o = LfWitness(o.w_ccs, None, o.f_coeff)
+            cm, xc = np.ascontiguousarray(case.cmi, np.uint64), flat(case.xi)
+            rc = P.lib.lf_fold_prove(P.h, C.byref(A), C.byref(a), cm.ctypes.data, xc.ctypes.data, C.byref(i),
+                                     C.byref(O_), C.byref(o), C.byref(PM), LA.REPR_CANONICAL)
+            return rc, P.lib.lf_prover_last_error(P.h).decode()
+
+        short = acc_dict(case.acc)
+        short["u"] = short["u"][:-d]  # t - 1 elements
+        for kw, code, text in ((dict(acc=short), LF_ERR_INCORRECT_LENGTH, "accumulator LCCCS sizes"),
+                               (dict(null_f_out=True), LF_ERR_INVALID_ARG, "missing witness buffer"),
+                               (dict(null_y1=True), LF_ERR_INVALID_ARG, "missing decomposition proof buffer")):
+            rc, msg = call(**kw)
+            assert rc == code and text in msg, (kw.keys(), rc, msg)
+            case.check(*case.fold())
     finally:
         ctx.close()
 

@@ -700,7 +700,9 @@ int lf_memtree_audit(lf_ctx *ctx, size_t pages, size_t words_per_page, const uin
  * length + items; structs = fields in declaration order. LCCCS: the reference
  * derives no CanonicalSerialize for it (arith.rs:193-194), so its layout is this
  * project's own, written by the same rules. repr describes the caller's words.
- * out == NULL (or too small: LF_ERR_INCORRECT_LENGTH) still returns the size. */
+ * out == NULL (or too small: LF_ERR_INCORRECT_LENGTH) still returns the size.
+ * Both directions at every supported ring: lf_lcccs_deserialize and
+ * lf_lfproof_deserialize (declared below lf_fold_verify) read the bytes back. */
 typedef struct {
   const uint64_t *elems; /* n ring elements (d words each) */
   size_t n;
@@ -924,8 +926,14 @@ int lf_fold_replay_samples(const lf_ccs_desc *ccs, const lf_params *pr, const lf
                            lf_replay_vars *out, int repr);
 /* NIFSVerifier::verify (latticefold/src/nifs.rs:117-162) over the zkvm's public-input
  * absorption, as main.rs:408-426 (verify_folding, the `debug` feature) runs it after every
- * fold(): on the host, no device needed. LF_OK with the folded LCCCS in `out` (r s, v tau,
- * cm kappa, u t, x_w l, h 1), or LF_ERR_VERIFICATION with the failed check in *failed. */
+ * fold(): on the host, no device needed, at every supported ring (lf_ring_supported). At
+ * X^d + 1 the base ring is Fq (tau = 1): a challenge is one transcript sample and its
+ * re-observation, broadcast into all d slots, as lf_fold_prove draws them. LF_OK with the
+ * folded LCCCS in `out` (r s, v tau, cm kappa, u t, x_w l, h 1), or LF_ERR_VERIFICATION with
+ * the failed check in *failed (the checks run in the enum's order). pr->d != acc->d is
+ * LF_ERR_INVALID_ARG, any other degree LF_ERR_UNSUPPORTED_RING, an accumulator whose slices
+ * are not (s, tau, kappa >= 1, t, l) long LF_ERR_INCORRECT_LENGTH; every proof buffer has the
+ * length lf_lfproof_shape gives (lf_lfproof_deserialize checks a received one). */
 enum lf_verify_check {
   LF_VERIFY_OK = 0,
   LF_VERIFY_LIN_SUMCHECK = 1,  /* a linearization sumcheck round: p(0) + p(1) != claim */
@@ -939,6 +947,28 @@ enum lf_verify_check {
 };
 int lf_fold_verify(const lf_ccs_desc *ccs, const lf_params *pr, const lf_lcccs *acc, const uint64_t *cm_i,
                    const uint64_t *x_ccs, const lf_lfproof_mut *proof, lf_lcccs_mut *out, int *failed, int repr);
+/* The wire section's readers (here, after the types they take): reading a proof back. The
+ * shape (ccs: t, m, l, degree; pr: d, K, b_small; kappa) fixes every length an LFProof carries: s = log2 m rounds of degree + 2 and 2 b_small + 1
+ * evaluations, K decomposed instances a side of t, tau, l + 1 and kappa elements, 2K thetas of
+ * tau and etas of t (tau = 3 at d = 24, else 1).
+ * lf_lfproof_shape: ring elements of each lf_lfproof_mut pointer for this shape, in the struct's
+ * order (lin_sumcheck, lin_v, lin_u, u_s[0], u_s[1], v_s[0], v_s[1], x_s[0], x_s[1], y_s[0],
+ * y_s[1], fold_sumcheck, theta_s, eta_s); returns their sum, 0 for a shape that is none (an
+ * unsupported d, m no power of two, a zero or absurd count). Reads only the fields named above
+ * (ccs->c, S_off and S_idx may be NULL). Host only.
+ * lf_lfproof_deserialize: the inverse of lf_lfproof_serialize for that shape: parses into buf
+ * (buf_elems u64 >= shape sum x d); out points into it and can go straight into lf_fold_verify.
+ * Every length in the bytes must equal the shape's (it is compared before anything is sized or
+ * indexed by it); a differing length, a short buffer, trailing bytes, a non-canonical word
+ * (>= p) and a too small buf are LF_ERR_INCORRECT_LENGTH, a non-shape LF_ERR_INVALID_ARG. */
+size_t lf_lfproof_shape(const lf_ccs_desc *ccs, const lf_params *pr, size_t kappa, size_t counts[14]);
+int lf_lfproof_deserialize(const uint8_t *in, size_t len, const lf_ccs_desc *ccs, const lf_params *pr,
+                           size_t kappa, int repr, uint64_t *buf, size_t buf_elems, lf_lfproof_mut *out);
+/* rot_lin_combination (cyclotomic-rings rotation.rs:84-101) on the host, the v_0 of the verifier's
+ * folded LCCCS: rho_coeff [n][d] coefficient form, theta [n][tau d] -> v0 [tau d]. At X^d + 1 it
+ * is ICRT(sum_i CRT(rho_i) (.) CRT(Theta_i)), Theta_i = theta_i's words read as coefficients,
+ * through a host negacyclic transform (slot k = f(psi^(2k+1))): O(n d log d). */
+int lf_rot_lin_combination(int d, const uint64_t *rho_coeff, const uint64_t *theta, size_t n, uint64_t *v0, int repr);
 /* every value the last lf_fold_prove sampled from its transcript (count returned, up to cap copied) */
 size_t lf_prover_samples(const lf_prover *prover, uint64_t *out, size_t cap);
 /* fold() then generate_verification_witness_vars (main.rs:175-185) in one call: lf_fold_prove,

@@ -998,7 +998,8 @@ def fold_verify(params: LfParams, t: int, m: int, l: int, degree: int, c, S, kap
                 proof: dict, repr: int = REPR_CANONICAL) -> dict:
     """NIFSVerifier::verify of a fold() proof (lf_fold_verify; zkvm main.rs:408-426): the
     folded LCCCS dict {r, v, cm, u, x_w, h}, or VerificationError naming the failed check.
-    Host only (Phi_72)."""
+    Host only, no GPU involved, at every supported ring (params.d: Phi_72 or X^d + 1). proof:
+    the dict Prover.fold_prove returns, or wire.deserialize_lfproof's of received bytes."""
     from ._lib import LfCcsDesc, LfLcccs, LfLcccsMut, LfLfproofMut, LfRingSlice
     lib, d = load(), params.d
     s, q = m.bit_length() - 1, len(S)
@@ -1030,6 +1031,17 @@ def fold_verify(params: LfParams, t: int, m: int, l: int, degree: int, c, S, kap
     if rc:
         raise LfError(rc, "lf_fold_verify: " + lib.lf_status_string(rc).decode())
     out["x_w"] = out["x_w"][:l * d]
+    return out
+
+
+def rot_lin_combination(rho_coeff, theta, d: int, repr: int = REPR_CANONICAL) -> np.ndarray:
+    """lf_rot_lin_combination (cyclotomic-rings rotation.rs:84-101) on the host, as the verifier
+    forms v_0: rho_coeff [n][d] coefficient form, theta [n][tau d] -> v0 [tau d]."""
+    lib, rc_, th = load(), _u64(rho_coeff).ravel(), _u64(theta).ravel()
+    out = np.zeros((3 if d == 24 else 1) * d, np.uint64)
+    rc = lib.lf_rot_lin_combination(d, _ptr(rc_), _ptr(th), rc_.size // d, _ptr(out), repr)
+    if rc:
+        raise LfError(rc, "lf_rot_lin_combination: " + lib.lf_status_string(rc).decode())
     return out
 
 

@@ -213,6 +213,10 @@ SIGNATURES = {
                            C.POINTER(LfLfproofMut), C.POINTER(LfReplayVars), I]),
     "lf_fold_verify": (I, [C.POINTER(LfCcsDesc), C.POINTER(LfParams), C.POINTER(LfLcccs), VP, VP,
                            C.POINTER(LfLfproofMut), C.POINTER(LfLcccsMut), C.POINTER(I), I]),
+    "lf_lfproof_shape": (SZ, [C.POINTER(LfCcsDesc), C.POINTER(LfParams), SZ, C.POINTER(SZ * 14)]),
+    "lf_lfproof_deserialize": (I, [VP, SZ, C.POINTER(LfCcsDesc), C.POINTER(LfParams), SZ, I, VP, SZ,
+                                   C.POINTER(LfLfproofMut)]),
+    "lf_rot_lin_combination": (I, [I, VP, VP, SZ, VP, I]),
     "lf_fold_replay_samples": (I, [C.POINTER(LfCcsDesc), C.POINTER(LfParams), C.POINTER(LfLcccs), VP, VP,
                                    C.POINTER(LfLfproofMut), VP, SZ, C.POINTER(LfReplayVars), I]),
     "lf_prover_samples": (SZ, [VP, VP, SZ]),

@@ -140,4 +140,77 @@ int lf_lfproof_serialize(const lf_lfproof *p, int repr, uint8_t *out, size_t cap
   return w.overflow ? LF_ERR_INCORRECT_LENGTH : LF_OK;
 }
 
+size_t lf_lfproof_shape(const lf_ccs_desc *ccs, const lf_params *pr, size_t kappa, size_t counts[14]) {
+  if (!ccs || !pr || !counts) return 0;
+  const int d = pr->d;
+  const size_t m = ccs->m, B = (size_t)1 << 32;  // every factor below 2^32 and s <= 63: no product wraps
+  if (d != 24 && (d < 16 || d > 4096 || (d & (d - 1)))) return 0;
+  if (ccs->t < 1 || ccs->degree < 1 || pr->K < 1 || pr->b_small < 1 || pr->b_small >= B / 4 || !m || (m & (m - 1)) ||
+      ccs->l >= B / 2 || !kappa || kappa >= B)
+    return 0;
+  size_t s = 0;
+  while (((size_t)1 << s) < m) s++;
+  const size_t tau = d == 24 ? 3 : 1, t = ccs->t, K = pr->K, L1 = ccs->l + 1;
+  const size_t c[14] = {s * ((size_t)ccs->degree + 2), tau, t, K * t, K * t, K * tau, K * tau, K * L1, K * L1,
+                        K * kappa, K * kappa, s * (2 * (size_t)pr->b_small + 1), 2 * K * tau, 2 * K * t};
+  size_t sum = 0;
+  for (int i = 0; i < 14; i++) {
+    if (c[i] > SIZE_MAX / 8 / 4096 / 16) return 0;
+    counts[i] = c[i];
+    sum += c[i];
+  }
+  return sum;
+}
+
+int lf_lfproof_deserialize(const uint8_t *in, size_t len, const lf_ccs_desc *ccs, const lf_params *pr, size_t kappa,
+                           int repr, uint64_t *buf, size_t buf_elems, lf_lfproof_mut *out) {
+  if (!in || !ccs || !pr || !buf || !out || (repr != LF_REPR_CANONICAL && repr != LF_REPR_MONTGOMERY))
+    return LF_ERR_INVALID_ARG;
+  size_t n[14];
+  const size_t total = lf_lfproof_shape(ccs, pr, kappa, n);
+  if (!total) return LF_ERR_INVALID_ARG;
+  const size_t d = pr->d, K = pr->K, tau = n[1], t = n[2], L1 = n[7] / K;
+  if (buf_elems / d < total) return LF_ERR_INCORRECT_LENGTH;
+  // the shape fixes the byte count too: the words, and one u64 per Vec (the two sumchecks'
+  // 1 + s each, lin_v, lin_u, four Vec<Vec> of K a side, theta_s and eta_s of 2K)
+  const size_t s = n[11] / (2 * (size_t)pr->b_small + 1), nvec = 2 * (1 + s) + 2 + 8 * (1 + K) + 2 * (1 + 2 * K);
+  if (len != 8 * (total * d + nvec)) return LF_ERR_INCORRECT_LENGTH;
+  uint64_t *at[14];  // where each lf_lfproof_mut pointer's elements go, in the struct's order
+  for (size_t i = 0, off = 0; i < 14; off += n[i++] * d) at[i] = buf + off;
+  Reader r{in, len, 0, repr};
+  // every length the bytes carry is compared with the shape's before anything is read by
+  // it, so the writes below stay inside the `total` elements checked above
+  auto vec = [&](uint64_t *dst, size_t elems) {  // Vec<R> of exactly `elems` ring elements
+    if (r.u64() != elems || r.bad) return false;
+    if ((len - r.pos) / 8 / d < elems) return false;
+    for (size_t i = 0; i < elems * d; i++) dst[i] = r.fq();
+    return !r.bad;
+  };
+  auto vecvec = [&](uint64_t *dst, size_t outer, size_t inner) {  // Vec<Vec<R>>, [outer][inner]
+    if (r.u64() != outer || r.bad) return false;
+    for (size_t i = 0; i < outer; i++)
+      if (!vec(dst + i * inner * d, inner)) return false;
+    return true;
+  };
+  bool ok = vecvec(at[0], s, (size_t)ccs->degree + 2) && vec(at[1], tau) && vec(at[2], t);
+  for (int side = 0; side < 2 && ok; side++)
+    ok = vecvec(at[3 + side], K, t) && vecvec(at[5 + side], K, tau) && vecvec(at[7 + side], K, L1) &&
+         vecvec(at[9 + side], K, kappa);
+  ok = ok && vecvec(at[11], s, 2 * (size_t)pr->b_small + 1) && vecvec(at[12], 2 * K, tau) && vecvec(at[13], 2 * K, t);
+  if (!ok || r.pos != len) return LF_ERR_INCORRECT_LENGTH;
+  out->lin_sumcheck = at[0];
+  out->lin_v = at[1];
+  out->lin_u = at[2];
+  for (int side = 0; side < 2; side++) {
+    out->u_s[side] = at[3 + side];
+    out->v_s[side] = at[5 + side];
+    out->x_s[side] = at[7 + side];
+    out->y_s[side] = at[9 + side];
+  }
+  out->fold_sumcheck = at[11];
+  out->theta_s = at[12];
+  out->eta_s = at[13];
+  return LF_OK;
+}
+
 }  // extern "C"

@@ -1,5 +1,5 @@
 """The wire format of the accumulator and the folding proof (include/lf.h
-lf_lcccs_* / lf_lfproof_serialize): ark-serialize 0.5 CanonicalSerialize of
+lf_lcccs_* / lf_lfproof_*): ark-serialize 0.5 CanonicalSerialize of
 the reference's types (latticefold/src/nifs.rs:28-34, arith.rs:192-206).
 Host-side byte layouts; numpy uint64 ring elements of d words each."""
 from __future__ import annotations
@@ -8,13 +8,18 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import LfDecompositionProof, LfLcccs, LfLfproof, LfRingSlice, load
+from ._lib import (LfCcsDesc, LfDecompositionProof, LfLcccs, LfLfproof, LfLfproofMut, LfParams, LfRingSlice,
+                   load)
 
 REPR_CANONICAL, REPR_MONTGOMERY = 0, 1
 
 
 class LfError(RuntimeError):
-    pass
+    """.code: the lf.h status where a C call failed (7 = LF_ERR_INCORRECT_LENGTH), else None"""
+
+    def __init__(self, msg: str, code: int | None = None):
+        super().__init__(msg)
+        self.code = code
 
 
 def _slice(a, d, keep):
@@ -57,7 +62,7 @@ def deserialize_lcccs(data: bytes, d: int, repr=REPR_CANONICAL) -> dict:
     rc = load().lf_lcccs_deserialize(raw.ctypes.data_as(C.c_void_p), raw.size, d, repr,
                                      buf.ctypes.data_as(C.c_void_p), buf.size, C.byref(out))
     if rc:
-        raise LfError(f"deserialize rc={rc}")
+        raise LfError(f"deserialize rc={rc}", rc)
     base = buf.ctypes.data
 
     def take(s):
@@ -91,3 +96,38 @@ def serialize_lfproof(d, lin_sumcheck, lin_rounds, lin_evals, lin_v, lin_u, dec,
     p.theta_s, p.n_theta = _slices(theta_s, d, keep)
     p.eta_s, p.n_eta = _slices(eta_s, d, keep)
     return _run(load().lf_lfproof_serialize, C.byref(p), repr)
+
+
+PROOF_FIELDS = ("lin_sumcheck", "lin_v", "lin_u", "u_s", "v_s", "x_s", "y_s", "fold_sumcheck", "theta_s", "eta_s")
+
+
+def deserialize_lfproof(data: bytes, params: LfParams, t: int, m: int, l: int, degree: int, q: int, kappa: int,
+                        repr=REPR_CANONICAL) -> dict:
+    """lf_lfproof_deserialize: the bytes of an LFProof of the shape (params, t, m, l, degree,
+    kappa) fix, as the proof dict fold_verify takes (the flat buffers of lf_lfproof_mut; u_s,
+    v_s, x_s, y_s as [left, right]). Every length in the bytes must be the shape's: LfError
+    (code 7) otherwise, and for truncated bytes, trailing bytes and a word >= p."""
+    lib = load()
+    desc = LfCcsDesc(t, m, l, degree, q, None, None, None)
+    counts = (C.c_size_t * 14)()
+    total = lib.lf_lfproof_shape(C.byref(desc), C.byref(params), kappa, C.byref(counts))
+    if not total:
+        raise LfError("lf_lfproof_shape: not a proof shape", 1)
+    d = params.d
+    raw = np.frombuffer(bytes(data), np.uint8).copy() if len(data) else np.zeros(1, np.uint8)
+    buf = np.zeros(total * d, np.uint64)
+    out = LfLfproofMut()
+    rc = lib.lf_lfproof_deserialize(raw.ctypes.data_as(C.c_void_p), len(data), C.byref(desc), C.byref(params), kappa,
+                                    repr, buf.ctypes.data_as(C.c_void_p), buf.size, C.byref(out))
+    if rc:
+        raise LfError(f"deserialize rc={rc}", rc)
+    base, n = buf.ctypes.data, iter(counts)
+
+    def take(ptr):
+        off = (ptr - base) // 8
+        return buf[off:off + next(n) * d].copy()
+    res = {}
+    for k in PROOF_FIELDS:  # the struct's order, which is the order of counts
+        v = getattr(out, k)
+        res[k] = take(v) if k not in ("u_s", "v_s", "x_s", "y_s") else [take(v[0]), take(v[1])]
+    return res

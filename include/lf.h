@@ -403,6 +403,22 @@ int lf_dev_gl_probe(lf_ctx *ctx, int op, const uint64_t *a, const uint64_t *b, i
  * nothing and leaves the decomposition-overflow state to lf_ctx_sync. In a batch every step's
  * context reports its own step. */
 int lf_ctx_fold_flag(lf_ctx *ctx, int *out);
+/* test aid: the launch plan of one sumcheck round over `half` = 2^(nv-1-i) points (round i of
+ * an nv-variable prove), as the round launchers themselves decide it (they call the same
+ * function). kind: the folding round, the unsplit linearization round (lf_sumcheck_prove and
+ * _ptrs, lf_dev_sumcheck_round) or the split-eq one (lf_sumcheck_prove_lin and _sparse); nf:
+ * the f_hat MLEs (nk tau) or the multisets (q) the sum may be split over. Needs no context and
+ * no device. out: [0] slots per block, [1] points per block, [2] grid.x, [3] grid.y, [4] the
+ * chunks nf is split over (grid.z; times the degree in the per-point kernel), [5] 1 if grid.x
+ * was capped, so a thread strides over several points, [6] split-eq only: 1 if the per-point
+ * kernel runs instead of the templated one, [7] split-eq only: the active points one block of
+ * the sparse round 0 takes. LF_ERR_INVALID_ARG for an unsupported d, half = 0 or nf < 1. */
+enum { LF_PLAN_FOLDING = 0, LF_PLAN_LIN = 1, LF_PLAN_LIN_EQ = 2 };
+int lf_sumcheck_round_plan(int d, size_t half, int nf, int kind, int out[8]);
+/* the same for the dot products of lf_dev_mle_evaluate(_eq) and lf_dev_fhat_evaluate(_eq) over
+ * n = 2^nv points: out: [0] slots per block, [1] points per block, [2] nsplit, the blocks
+ * along the points, [3] the passes of a thread's loop over its points */
+int lf_sumcheck_dot_plan(int d, size_t n, int out[4]);
 /* synthetic inputs: element i = SplitMix64(seed, i) re-mixed until < p */
 int lf_dev_fill_uniform(lf_ctx *ctx, uint64_t *out, size_t n, uint64_t seed);
 /* out[c] = sum_r in[r][c] mod p  (reduce of all-gathered accumulators) */
@@ -869,6 +885,11 @@ int lf_dev_fhat_evaluate_eq(lf_ctx *ctx, int d, const uint64_t *f_coeff, size_t 
 /* io[x] += sum_m coef[m] (.) mles[m][x] over 2^nv points (stride 0 = 2^nv d) */
 int lf_dev_mle_lincomb(lf_ctx *ctx, int d, const uint64_t *mles, size_t stride, int nm, int nv, const uint64_t *coef,
                        uint64_t *io);
+/* io[x] += sum_(k, j) coef[k tau + j] (.) fhat_(k, j)[x] over 2^nv points, the f_hat MLEs of nw
+ * witnesses read from their digit coefficient rows (every value 0, 1 or -1; wstride u64 apart,
+ * 0 = N d; zero past N <= 2^nv); coef: nw tau NTT elements on the device */
+int lf_dev_fhat_lincomb_digits(lf_ctx *ctx, int d, const uint64_t *f_coeff, size_t N, size_t wstride, int nw, int nv,
+                               const uint64_t *coef, uint64_t *io);
 int lf_ctx_device(const lf_ctx *ctx);
 
 /* generate_verification_witness_vars (zkvm/src/zk_latticefold.rs:111-148): the

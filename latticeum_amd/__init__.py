@@ -41,6 +41,29 @@ def ring_supported(d: int) -> bool:
     return bool(load().lf_ring_supported(int(d)))
 
 
+PLAN_FOLDING, PLAN_LIN, PLAN_LIN_EQ = 0, 1, 2
+
+
+def sumcheck_round_plan(d: int, half: int, nf: int, kind: int) -> dict:
+    """test aid (lf_sumcheck_round_plan, needs no Context): the launch plan of a sumcheck round
+    over `half` points, as the launchers decide it"""
+    out = (C.c_int * 8)()
+    rc = load().lf_sumcheck_round_plan(d, half, nf, kind, C.byref(out))
+    if rc != 0:
+        raise LfError(rc, f"lf_sumcheck_round_plan(d={d}, half={half}, nf={nf}, kind={kind})")
+    keys = ("spb", "ppb", "gx", "gy", "nchunk", "capped", "per_point", "sparse_block_points")
+    return dict(zip(keys, (int(x) for x in out)))
+
+
+def sumcheck_dot_plan(d: int, n: int) -> dict:
+    """test aid (lf_sumcheck_dot_plan, needs no Context): how the MLE dot products split n points"""
+    out = (C.c_int * 4)()
+    rc = load().lf_sumcheck_dot_plan(d, n, C.byref(out))
+    if rc != 0:
+        raise LfError(rc, f"lf_sumcheck_dot_plan(d={d}, n={n})")
+    return dict(zip(("spb", "ppb", "nsplit", "passes"), (int(x) for x in out)))
+
+
 def _u64(a) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(a, dtype=np.uint64))
 
@@ -334,6 +357,29 @@ class Context:
     def dev_mle_evaluate(self, d: int, mles, nm: int, nv: int, point, out):
         self.check(self.lib.lf_dev_mle_evaluate(self.h, d, _dptr(mles), nm, nv, _dptr(point), _dptr(out)))
 
+    def dev_mle_evaluate_eq(self, d: int, mles, nm: int, nv: int, eq, out):
+        """dev_mle_evaluate from the point's eq table (2^nv elements, dev_eq_table)"""
+        self.check(self.lib.lf_dev_mle_evaluate_eq(self.h, d, _dptr(mles), nm, nv, _dptr(eq), _dptr(out)))
+
+    def dev_fhat_evaluate(self, d: int, f_coeff, N: int, wstride: int, nw: int, nv: int, point, out):
+        """the f_hat MLEs of nw witnesses at a point, from their f_coeff rows (wstride u64 apart,
+        0 = N d): out [nw][tau][d]"""
+        self.check(self.lib.lf_dev_fhat_evaluate(self.h, d, _dptr(f_coeff), N, wstride, nw, nv, _dptr(point),
+                                                 _dptr(out)))
+
+    def dev_fhat_evaluate_eq(self, d: int, f_coeff, N: int, wstride: int, nw: int, nv: int, eq, out):
+        self.check(self.lib.lf_dev_fhat_evaluate_eq(self.h, d, _dptr(f_coeff), N, wstride, nw, nv, _dptr(eq),
+                                                    _dptr(out)))
+
+    def dev_mle_lincomb(self, d: int, mles, stride: int, nm: int, nv: int, coef, io):
+        """io[x] += sum_m coef[m] (.) mles[m][x] over 2^nv points (stride 0 = 2^nv d)"""
+        self.check(self.lib.lf_dev_mle_lincomb(self.h, d, _dptr(mles), stride, nm, nv, _dptr(coef), _dptr(io)))
+
+    def dev_fhat_lincomb_digits(self, d: int, f_coeff, N: int, wstride: int, nw: int, nv: int, coef, io):
+        """io[x] += sum_(k, j) coef[k tau + j] (.) fhat_(k, j)[x] from nw witnesses' digit rows"""
+        self.check(self.lib.lf_dev_fhat_lincomb_digits(self.h, d, _dptr(f_coeff), N, wstride, nw, nv, _dptr(coef),
+                                                       _dptr(io)))
+
     def dev_mle_fix_first(self, d: int, src, src_stride: int, nm: int, nv: int, r_base, out, out_stride: int):
         r = _u64(r_base)
         self.check(self.lib.lf_dev_mle_fix_first(self.h, d, _dptr(src), src_stride, nm, nv, _ptr(r), _dptr(out),
@@ -352,6 +398,18 @@ class Context:
         rnd = np.zeros(nv * tau, np.uint64)
         self.check(self.lib.lf_sumcheck_prove(self.h, transcript.h, C.byref(comb.s), _dptr(mles), nm, nv, d,
                                               degree, _ptr(proof), _ptr(rnd)))
+        return proof, rnd
+
+    def sumcheck_prove_ptrs(self, transcript: "Poseidon2Transcript", comb: "Comb", mles, nv: int, d: int,
+                            degree: int, work):
+        """sumcheck_prove over MLEs that stay where they are (lf_sumcheck_prove_ptrs): mles a
+        list of device tensors (2^nv elements each, read only), work len(mles) x 2^(nv-2) elements"""
+        tau = 3 if d == 24 else 1
+        proof = np.zeros(nv * (degree + 1) * d, np.uint64)
+        rnd = np.zeros(nv * tau, np.uint64)
+        ptrs = (C.c_void_p * len(mles))(*[_dptr(m) for m in mles])
+        self.check(self.lib.lf_sumcheck_prove_ptrs(self.h, transcript.h, C.byref(comb.s), ptrs, len(mles), nv, d,
+                                                   degree, _dptr(work), _ptr(proof), _ptr(rnd)))
         return proof, rnd
 
     def sumcheck_prove_fold_digits(self, transcript: "Poseidon2Transcript", comb: "Comb", mles5, fc0, fc1, K: int,

@@ -139,6 +139,9 @@ SIGNATURES = {
     "lf_dev_poseidon2_permute_rounds": (I, [VP, VP, SZ, I]),
     "lf_dev_gl_probe": (I, [VP, I, VP, VP, I, I, VP, SZ]),
     "lf_ctx_fold_flag": (I, [VP, C.POINTER(I)]),
+    "lf_sumcheck_round_plan": (I, [I, SZ, I, I, C.POINTER(I * 8)]),
+    "lf_sumcheck_dot_plan": (I, [I, SZ, C.POINTER(I * 4)]),
+    "lf_dev_fhat_lincomb_digits": (I, [VP, I, VP, SZ, SZ, I, I, VP, VP]),
     "lf_dev_fill_uniform": (I, [VP, VP, SZ, U64]),
     "lf_dev_modp_sum": (I, [VP, VP, I, SZ, VP]),
     "lf_dev_limb_split": (I, [VP, VP, SZ, VP, VP]),

@@ -138,12 +138,11 @@ int sumcheck_run_lin(lf_ctx *c, lf_transcript *t, const lf_comb *cb, const lfk::
   const size_t n = (size_t)1 << nv;
   size_t part = 0;
   for (size_t h = n / 2; h >= 1; h /= 2) part = std::max(part, lfk::round_partial_elems(d, h, nq, cb->q));
-  // sparse round 0: block g runs multiset bms[g] over act[boff[g] .. bend[g]), about 8
-  // points per thread
+  // sparse round 0: block g runs multiset bms[g] over act[boff[g] .. bend[g])
   std::vector<uint32_t> blk;  // bms | boff | bend
   int nblk = 0;
   if (act) {
-    const uint32_t per = (uint32_t)lfk::round_lin_sparse_ppb(d) * 8;
+    const uint32_t per = (uint32_t)lfk::round_lin_sparse_block_points(d);
     std::vector<uint32_t> bms, bo, be;
     for (int i = 0; i < cs.q; i++)
       for (uint32_t p = act_off[i]; p < act_off[i + 1]; p += per) {
@@ -316,6 +315,45 @@ int lf_dev_mle_lincomb(lf_ctx *c, int d, const uint64_t *mles, size_t stride, in
   if (!ring_ok(d)) return fail(c, LF_ERR_UNSUPPORTED_RING, "unsupported ring degree");
   const size_t n = (size_t)1 << nv;
   LF_HIP(c, lfk::mle_lincomb(mles, stride ? stride : n * d, nm, coef, n, d, io, c->cur));
+  return LF_OK;
+}
+
+int lf_dev_fhat_lincomb_digits(lf_ctx *c, int d, const uint64_t *f_coeff, size_t N, size_t wstride, int nw, int nv,
+                               const uint64_t *coef, uint64_t *io) {
+  if (!c || !io || nw < 0 || nv < 0 || nv > 40 || (nw && (!coef || (N && !f_coeff)))) return LF_ERR_INVALID_ARG;
+  DevGuard g(c);
+  if (!ring_ok(d)) return fail(c, LF_ERR_UNSUPPORTED_RING, "unsupported ring degree");
+  if (N > ((size_t)1 << nv)) return fail(c, LF_ERR_INCORRECT_LENGTH, "N exceeds 2^nv");
+  if (!nw) return LF_OK;
+  LF_HIP(c, lfk::fhat_lincomb_digits(f_coeff, nw, N, wstride ? wstride : N * d, coef, nv, d, io, c->cur));
+  return LF_OK;
+}
+
+static_assert(LF_PLAN_FOLDING == lfk::ROUND_FOLDING && LF_PLAN_LIN == lfk::ROUND_LIN &&
+                  LF_PLAN_LIN_EQ == lfk::ROUND_LIN_EQ,
+              "lf.h's plan kinds are the launchers' round kinds");
+int lf_sumcheck_round_plan(int d, size_t half, int nf, int kind, int out[8]) {
+  if (!out || !ring_ok(d) || !half || nf < 1 || kind < LF_PLAN_FOLDING || kind > LF_PLAN_LIN_EQ)
+    return LF_ERR_INVALID_ARG;
+  const lfk::RoundPlan pl = lfk::round_plan(d, half, nf, kind);
+  out[0] = pl.spb;
+  out[1] = pl.ppb;
+  out[2] = (int)pl.gx;
+  out[3] = (int)pl.gy;
+  out[4] = (int)pl.nchunk;
+  out[5] = pl.capped;
+  out[6] = pl.per_point;
+  out[7] = kind == LF_PLAN_LIN_EQ ? (int)lfk::round_lin_sparse_block_points(d) : 0;
+  return LF_OK;
+}
+
+int lf_sumcheck_dot_plan(int d, size_t n, int out[4]) {
+  if (!out || !ring_ok(d) || !n) return LF_ERR_INVALID_ARG;
+  const lfk::DotPlan pl = lfk::dot_plan(d, n);
+  out[0] = pl.spb;
+  out[1] = pl.ppb;
+  out[2] = pl.nsplit;
+  out[3] = (int)std::min(pl.passes, (size_t)INT32_MAX);
   return LF_OK;
 }
 

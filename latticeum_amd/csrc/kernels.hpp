@@ -298,7 +298,23 @@ hipError_t assemble_z(const uint64_t *x, const uint64_t *w, int nz, size_t l1, s
 // ptrs (device, nm pointers, optional): MLE m at ptrs[m] instead of in + m in_stride
 hipError_t mle_fix_first(const uint64_t *in, size_t in_stride, int nm, size_t half, int d, const uint64_t *r_base,
                          uint64_t *out, size_t out_stride, hipStream_t st, const uint64_t *const *ptrs = nullptr);
-// nf: the f_hat MLEs the folding round may split over chunks (1 for linearization)
+// The launch plan of a round-sum kernel over `half` points, decided in one place: every
+// launcher below, round_partial_elems and the host diagnostic lf_sumcheck_round_plan read it.
+// nf: the f_hat MLEs (folding) or multisets (linearization) the sum may split over chunks
+enum RoundKind { ROUND_FOLDING = 0, ROUND_LIN = 1, ROUND_LIN_EQ = 2 };
+struct RoundPlan {
+  int spb, ppb;              // slots and points per block
+  unsigned gx, gy, nchunk;   // grid: blocks along the points, along the slots, chunks (grid.z)
+  bool capped;               // gx was cut to the cap: a thread strides over several points
+  bool per_point;            // ROUND_LIN_EQ only: k_round_lin_eq_pt runs (grid.z = nchunk degree)
+};
+RoundPlan round_plan(int d, size_t half, int nf, int kind);
+// mle_dot / fhat_dot over n points: nsplit blocks along the points, each thread `passes` of them
+struct DotPlan {
+  int spb, ppb, nsplit;
+  size_t passes;
+};
+DotPlan dot_plan(int d, size_t n);
 size_t round_partial_elems(int d, size_t half, int nevals, int nf);
 hipError_t fold_weights(const uint64_t *mu, int nk, int tau, int d, uint64_t *w, hipStream_t st);
 // evals [2 bsmall + 1][d]: the folding polynomial's round sums over `half` points;
@@ -332,7 +348,7 @@ hipError_t round_lin_eq_sparse(const uint64_t *const *ptrs, const uint64_t *E, c
                                int degree, const uint32_t *act, const int *bms, const uint32_t *boff,
                                const uint32_t *bend, int nblk, int d, uint64_t *partial, uint64_t *evals,
                                hipStream_t st);
-size_t round_lin_sparse_ppb(int d);  // points per block pass of round_lin_eq_sparse
+size_t round_lin_sparse_block_points(int d);  // active points one block of round_lin_eq_sparse takes
 // E_next[b] = E[2b] + E[2b+1] for b < half (whole ring elements)
 hipError_t pair_sum(const uint64_t *E, size_t half, int d, uint64_t *out, hipStream_t st);
 size_t mle_eval_partial_elems(int d, int nm);

@@ -462,10 +462,13 @@ __global__ void __launch_bounds__(RT) k_round_lin(const uint64_t *mles, size_t s
 // api_sumcheck.hip). p(e) is the same field element either way, so the messages are
 // the reference's (prover.rs:62-168 over linearization/utils.rs:63-104).
 //
-// A multiset's product c_i prod_f (a_f + d_f e) is formed in two groups in
-// coefficient form (c_i and the first KA factors; the other KB), each walked
-// along e = 0 .. NQ-1 by forward differences, and the groups multiplied
-// pointwise: for |S_i| = 7 that is 20 + 10 + 8 products instead of 6 + 5 x 9.
+// A multiset's product c_i prod_f (a_f + d_f e): c_i and the first one or two
+// factors are multiplied in coefficient form and walked along e = 0 .. NQ-1 by
+// forward differences (multiset_add<., ., 1, 0> and <., ., 2, 0>, the only
+// instantiations); every further factor is multiplied in at the NQ points, weakly
+// reduced along the chain and canonicalised once before the sum. multiset_add's
+// second group (KB > 0) and the degree-3 and -4 forms of poly_mul_lin and
+// poly_to_diff are not instantiated by any kernel.
 
 // c <- c (a + d e) for a degree-M polynomial in coefficient form (in place, from the top;
 // each new coefficient one lazy multiply-accumulate pair)
@@ -854,12 +857,14 @@ hipError_t mle_fix_first(const uint64_t *in, size_t in_stride, int nm, size_t ha
 constexpr size_t FILL_THREADS = (size_t)1 << 18;
 // at or below this many (point, slot) threads the linearization round runs per evaluation point
 constexpr size_t PT_THREADS = (size_t)1 << 13;
-static void round_geom(int d, size_t half, int nf, int &spb, dim3 &grid) {
+RoundPlan round_plan(int d, size_t half, int nf, int kind) {
+  RoundPlan pl;
   const int ns = d / slot_words(d);
-  spb = ns < RT ? ns : RT;
-  const int ppb = RT / spb;
-  size_t bx = (half + ppb - 1) / ppb;
+  pl.spb = ns < RT ? ns : RT;
+  pl.ppb = RT / pl.spb;
+  size_t bx = (half + pl.ppb - 1) / pl.ppb;
   const size_t cap = 1024;  // partial sums: at most this many blocks along the points
+  pl.capped = bx > cap;
   if (bx > cap) bx = cap;
   if (bx < 1) bx = 1;
   size_t nchunk = 1;
@@ -868,13 +873,26 @@ static void round_geom(int d, size_t half, int nf, int &spb, dim3 &grid) {
     nchunk = (FILL_THREADS + threads - 1) / threads;
     if (nchunk > (size_t)nf) nchunk = nf;
   }
-  grid = dim3((unsigned)bx, (unsigned)(ns / spb), (unsigned)nchunk);
+  pl.gx = (unsigned)bx;
+  pl.gy = (unsigned)(ns / pl.spb);
+  pl.nchunk = (unsigned)nchunk;
+  pl.per_point = kind == ROUND_LIN_EQ && threads <= PT_THREADS;  // few points: a thread per (point, slot, chunk, e)
+  return pl;
 }
+static dim3 plan_grid(const RoundPlan &pl) { return dim3(pl.gx, pl.gy, pl.nchunk); }
 size_t round_partial_elems(int d, size_t half, int nevals, int nf) {
-  int spb;
-  dim3 g;
-  round_geom(d, half, nf, spb, g);
-  return (size_t)g.x * g.z * nevals * d;
+  const RoundPlan pl = round_plan(d, half, nf, ROUND_FOLDING);  // the grid is the same for every kind
+  return (size_t)pl.gx * pl.nchunk * nevals * d;
+}
+DotPlan dot_plan(int d, size_t n) {
+  DotPlan pl;
+  const int ns = d / slot_words(d);
+  pl.spb = ns < RT ? ns : RT;
+  pl.ppb = RT / pl.spb;
+  const size_t sx = (n + pl.ppb - 1) / pl.ppb;
+  pl.nsplit = (int)(sx < 64 ? sx : 64);
+  pl.passes = pl.nsplit ? (sx + pl.nsplit - 1) / pl.nsplit : 0;
+  return pl;
 }
 
 hipError_t fold_weights(const uint64_t *mu, int nk, int tau, int d, uint64_t *w, hipStream_t st) {
@@ -889,9 +907,9 @@ hipError_t fold_weights(const uint64_t *mu, int nk, int tau, int d, uint64_t *w,
 hipError_t round_folding(const uint64_t *mles, size_t stride, int nf, const uint64_t *w, int bsmall, size_t half, int d,
                          uint64_t *partial, uint64_t *evals, hipStream_t st) {
   if (bsmall < 1 || bsmall > 4 || !half) return hipErrorInvalidValue;
-  int spb;
-  dim3 grid;
-  round_geom(d, half, nf, spb, grid);
+  const RoundPlan pl = round_plan(d, half, nf, ROUND_FOLDING);
+  const int spb = pl.spb;
+  const dim3 grid = plan_grid(pl);
 #define LF_RF(TB, BS)                                                                                           \
   hipLaunchKernelGGL((k_round_folding<TB, BS>), grid, dim3(RT), 0, st, mles, stride, nf, w, half, d, spb, partial)
 #define LF_RF_BS(TB)          \
@@ -920,9 +938,9 @@ hipError_t round_folding0_digits(const uint64_t *mles, size_t stride, const uint
                                 size_t N, size_t wstride, int nf, const uint64_t *w, size_t half, int d,
                                 uint64_t *partial, uint64_t *evals, hipStream_t st) {
   if (!half) return hipErrorInvalidValue;
-  int spb;
-  dim3 grid;
-  round_geom(d, half, nf, spb, grid);
+  const RoundPlan pl = round_plan(d, half, nf, ROUND_FOLDING);
+  const int spb = pl.spb;
+  const dim3 grid = plan_grid(pl);
   if (slot_words(d) == 3)
     hipLaunchKernelGGL(k_round_folding0_digits<3>, grid, dim3(RT), 0, st, mles, stride, fc0, fc1, K, N, wstride, nf, w,
                        half, d, spb, partial);
@@ -973,9 +991,9 @@ hipError_t round_lin(const uint64_t *mles, size_t stride, int nm, const uint64_t
                      size_t half, int d, uint64_t *partial, uint64_t *evals, hipStream_t st,
                      const uint64_t *const *ptrs) {
   if (degree + 1 > MAX_EVALS || degree < 1 || !half) return hipErrorInvalidValue;
-  int spb;
-  dim3 grid;
-  round_geom(d, half, cs.q, spb, grid);
+  const RoundPlan pl = round_plan(d, half, cs.q, ROUND_LIN);
+  const int spb = pl.spb;
+  const dim3 grid = plan_grid(pl);
 #define LF_RL(TB, DG) \
   hipLaunchKernelGGL((k_round_lin<TB, DG>), grid, dim3(RT), 0, st, mles, stride, ptrs, nm, c, cs, half, d, spb, partial)
 #define LF_RL_DEG(TB)                          \
@@ -1009,10 +1027,10 @@ hipError_t round_lin_eq(const uint64_t *mles, size_t stride, const uint64_t *E, 
                         int degree, size_t half, int d, uint64_t *partial, uint64_t *evals, hipStream_t st,
                         const uint64_t *const *ptrs) {
   if (degree + 1 > MAX_EVALS || degree < 1 || !half) return hipErrorInvalidValue;
-  int spb;
-  dim3 grid;
-  round_geom(d, half, cs.q, spb, grid);
-  if (half * (size_t)(d / slot_words(d)) <= PT_THREADS) {  // few points: a thread per (point, slot, chunk, e)
+  const RoundPlan pl = round_plan(d, half, cs.q, ROUND_LIN_EQ);
+  const int spb = pl.spb;
+  const dim3 grid = plan_grid(pl);
+  if (pl.per_point) {
     const dim3 g2(grid.x, grid.y, grid.z * degree);
     if (slot_words(d) == 3)
       hipLaunchKernelGGL(k_round_lin_eq_pt<3>, g2, dim3(RT), 0, st, mles, stride, ptrs, E, c, cs, half, d, spb, degree,
@@ -1062,8 +1080,9 @@ hipError_t round_lin_eq_sparse(const uint64_t *const *ptrs, const uint64_t *E, c
                                const uint32_t *bend, int nblk, int d, uint64_t *partial, uint64_t *evals,
                                hipStream_t st) {
   if (degree + 1 > MAX_EVALS || degree < 1 || nblk < 1) return hipErrorInvalidValue;
-  const int ns = d / slot_words(d), spb = ns < RT ? ns : RT;
-  const dim3 grid((unsigned)nblk, (unsigned)(ns / spb), 1);
+  const RoundPlan pl = round_plan(d, 1, 1, ROUND_LIN_EQ);  // its block shape; the blocks are the caller's
+  const int spb = pl.spb;
+  const dim3 grid((unsigned)nblk, pl.gy, 1);
 #define LF_RLS(TB, NQ)                                                                                          \
   hipLaunchKernelGGL((k_round_lin_eq_sparse<TB, NQ>), grid, dim3(RT), 0, st, ptrs, E, c, cs, act, bms, boff, bend, \
                      d, spb, partial)
@@ -1092,10 +1111,8 @@ hipError_t round_lin_eq_sparse(const uint64_t *const *ptrs, const uint64_t *E, c
   hipLaunchKernelGGL(k_sum_partials, dim3((unsigned)len), dim3(256), 0, st, partial, nblk, len, evals);
   return hipGetLastError();
 }
-size_t round_lin_sparse_ppb(int d) {
-  const int ns = d / slot_words(d);
-  return RT / (ns < RT ? ns : RT);
-}
+// about 8 points per thread
+size_t round_lin_sparse_block_points(int d) { return (size_t)round_plan(d, 1, 1, ROUND_LIN_EQ).ppb * 8; }
 
 hipError_t pair_sum(const uint64_t *E, size_t half, int d, uint64_t *out, hipStream_t st) {
   const size_t n = half * d;
@@ -1110,9 +1127,8 @@ hipError_t mle_dot(const uint64_t *mles, size_t stride, int nm, const uint64_t *
                    uint64_t *partial, uint64_t *out, hipStream_t st) {
   if (!nm || !n) return hipSuccess;
   const int tb = slot_words(d), ns = d / tb;
-  const int spb = ns < RT ? ns : RT, ppb = RT / spb;
-  size_t sx = (n + ppb - 1) / ppb;
-  const int nsplit = (int)(sx < 64 ? sx : 64);
+  const DotPlan pl = dot_plan(d, n);
+  const int spb = pl.spb, nsplit = pl.nsplit;
   const dim3 grid((unsigned)nsplit, (unsigned)(ns / spb), (unsigned)nm);
   if (tb == 3)
     hipLaunchKernelGGL(k_mle_dot<3>, grid, dim3(RT), 0, st, mles, stride, eq, n, d, spb, nsplit, partial, nm);
@@ -1129,9 +1145,8 @@ hipError_t fhat_dot(const uint64_t *fc, size_t N, size_t wstride, int nw, const 
                     uint64_t *partial, uint64_t *out, hipStream_t st) {
   const int tb = slot_words(d), ns = d / tb, tau = tb == 3 ? 3 : 1, nm = nw * tau;
   if (!nw || !n) return hipSuccess;
-  const int spb = ns < RT ? ns : RT, ppb = RT / spb;
-  size_t sx = (n + ppb - 1) / ppb;
-  const int nsplit = (int)(sx < 64 ? sx : 64);
+  const DotPlan pl = dot_plan(d, n);
+  const int spb = pl.spb, nsplit = pl.nsplit;
   const dim3 grid((unsigned)nsplit, (unsigned)(ns / spb), (unsigned)nm);
   if (tb == 3)
     hipLaunchKernelGGL(k_fhat_dot<3>, grid, dim3(RT), 0, st, fc, N, wstride, eq, n, d, spb, nsplit, partial, nm);

@@ -191,8 +191,9 @@ def lin_eq_case(d, nv, sizes, seed):
 @pytest.mark.parametrize("d,nv,sizes", [(24, 6, [7, 1, 2, 0, 3]), (24, 5, [8, 5, 6, 4, 1]), (64, 4, [7, 2, 5]),
                                         (24, 1, [3, 2]), (1024, 3, [4, 7])])
 def test_linearization_prove_lin_matches_oracle(ctx, d, nv, sizes):
-    """lf_sumcheck_prove_lin (eq(beta) split off, pointer table, two-group products) gives
-    the oracle's proof over [mz..., eq(beta)], multisets of 0 .. 8 factors"""
+    """lf_sumcheck_prove_lin (eq(beta) split off, pointer table) gives the oracle's proof over
+    [mz..., eq(beta)], multisets of 0 .. 8 factors; at these sizes every round runs the
+    per-point kernel (the templated one: tests/test_gpu_sumcheck_paths.py)"""
     c, S, mz, beta = lin_eq_case(d, nv, sizes, 1000 + d + nv)
     degree = max(sizes) + 1
     mles = np.concatenate(mz + [O.eq_table(beta, nv, d)])

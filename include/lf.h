@@ -283,7 +283,7 @@ typedef struct {
   uint64_t *f_coeff, *f;       /* N each: Witness::from_w_ccs(w_ccs) */
   uint64_t *cm;                /* kappa: CCCS.cm = A f */
   uint64_t *fk_coeff[2];       /* [K][N] per side (0 = accumulator, 1 = new instance) */
-  uint64_t *fk[2];             /* [K][N]; both NULL on the fused X^1024+1 path: the decomposed planes then
+  uint64_t *fk[2];             /* [K][N]; both NULL on a fused X^d+1 path (d = 16 .. 512, 1024, 4096): the planes then
                                 * live only in the context's MFMA operand rows, which the fold reads
                                 * (they are transient in the reference too: compute_f_0, folding.rs:258) */
   uint64_t *wk[2];             /* [K][W] */
@@ -304,9 +304,24 @@ typedef struct {
    * d = 4096 (the fused path): N x K KiB, one byte per coefficient quad and plane
    * (bit b = the digit of coefficient a + 1024 b is nonzero, bit 4 + b = that
    * coefficient is negative; byte ((e K + k) 32 + r) 32 + j holds a = r + 32 j), and
-   * f_0 is folded from the operand rows. */
+   * f_0 is folded from the operand rows.
+   * d = 16, 32, 64, 128, 256, 512 (the fused path, taken only when planes are
+   * given or fk is NULL on both sides; K <= 15): N x 2 d bytes, the same 16-bit
+   * sign|magnitude word per coefficient, one format for the six degrees: an
+   * element is d / 2 u32, and word j (j < d / 2) of element e sits at e d / 2 + j
+   * and holds coefficient j in its low half and coefficient j + d / 2 in its high
+   * half. planes beside fk: both are written; with fk NULL f_0 is folded from the
+   * operand rows.
+   * d = 2048 has no packed form (sixteen elements' transform tile, 256 KiB, does
+   * not fit a compute unit's LDS): planes, or NULL fk, are refused there as before.
+   * lf_fold_step_planes_len gives the length of one side's buffer. */
   uint64_t *planes[2];
 } lf_fold_step_bufs;
+/* u64 words of one side's `planes` buffer for N elements (host only, no context):
+ * K N at d = 24, N d / 4 at d = 16 .. 512, 256 N at d = 1024, 128 K N at d = 4096;
+ * 0 where the step has no packed form (d = 2048 or an unsupported degree,
+ * b_small != 2, K > 15) */
+size_t lf_fold_step_planes_len(const lf_params *pr, size_t N);
 /* packed digit planes (lf_fold_step_bufs.planes) of N elements -> the Witness forms of
  * decompose_witness's outputs (decomposition.rs:162-167, arith.rs:324-338):
  * f_coeff_k [K][N] (digits mod p) and / or f_k [K][N] = CRT(f_coeff_k); either may be NULL */

@@ -36,6 +36,12 @@ def goldilocks_dp(d: int = 24) -> LfParams:
     return load().lf_goldilocks_dp(d)
 
 
+def fold_step_planes_len(params: LfParams, N: int) -> int:
+    """lf_fold_step_planes_len: u64 words of one side's packed `planes` buffer for N elements;
+    0: these parameters have no packed form (needs no Context)."""
+    return load().lf_fold_step_planes_len(C.byref(params), N)
+
+
 def ring_supported(d: int) -> bool:
     """lf_ring_supported: d is 24 or a power of two from 16 to 4096 (needs no Context)."""
     return bool(load().lf_ring_supported(int(d)))

@@ -259,6 +259,7 @@ SIGNATURES = {
     "lf_compute_x_s": (I, [VP, C.POINTER(LfParams), VP, SZ, VP, I]),
     "lf_dev_compute_x_s": (I, [VP, C.POINTER(LfParams), VP, SZ, VP]),
     "lf_fold_step_partial_len": (SZ, [VP, C.POINTER(LfParams)]),
+    "lf_fold_step_planes_len": (SZ, [C.POINTER(LfParams), SZ]),
     "lf_dev_fold_step_partial": (I, [VP, VP, C.POINTER(LfParams), SZ, C.POINTER(LfFoldStepBufs), VP]),
     "lf_dev_fold_step_finish": (I, [VP, VP, C.POINTER(LfParams), SZ, C.POINTER(LfFoldStepBufs), VP]),
     "lf_dev_fold_step_sharded": (I, [VP, VP, C.POINTER(LfParams), SZ, C.POINTER(LfFoldStepBufs), VP]),

@@ -30,8 +30,8 @@ struct PhaseTimer {
 //    the 2(K-1) commitments of commit_witnesses (:178-201), plus -- when
 //    `commit_f` is given (the device step) -- commit(z)'s A.f in the same pass
 //    over A (29 vectors, one read of A). Result v goes to dst[v]: commit(z)'s
-//    cm first, then y_s[k], s = 0, 1, k = 1 .. K-1. On the fused X^1024 + 1 and
-//    X^4096 + 1 decompositions vector 0 is side 1's plane-0 operand row instead
+//    cm first, then y_s[k], s = 0, 1, k = 1 .. K-1. On the fused X^d + 1
+//    decompositions (d = 16 .. 512, 1024, 4096) vector 0 is side 1's plane-0 operand row instead
 //    (z_plane0 below) and its result y_1[0]: no pass converts f.
 //  fold_finish: y_0 = cm - sum b^k y_k of both sides (cm1_out: side 1's y_0 is
 //    given and cm = sum b^k y_k is made instead), cm_0 = sum rho_i y_i,
@@ -43,8 +43,9 @@ bool n4k_ok(const Tables *t, int d, int lbs, int K) { return d == 4096 && lbs ==
 // Which decomposition fold_commit runs and how fold_finish then makes f_0. The fused
 // decompositions write their digit planes straight into the MFMA operand buffer; they
 // need a scheme with fragments in the column order grouped by this L (d = 4096: in
-// the quarter-major operand slots).
-enum class Decomp { Plain, Fused1024, Fused24, Fused4k };
+// the quarter-major operand slots). FusedPow2 (d = 16 .. 512, decompose_pow2.hip) is
+// the one a caller opts into: with f_k buffers and no planes those degrees stay Plain.
+enum class Decomp { Plain, Fused1024, Fused24, Fused4k, FusedPow2 };
 struct StepPlan {
   Decomp dec = Decomp::Plain;
   FoldPath path = FoldPath::Ntt;  // Masks24*: when the decomposition then reports its masks
@@ -65,6 +66,11 @@ StepPlan step_plan(const lf_ajtai *aj, const lf_params *pr, int lbs, const Table
   } else if (grouped && aj->geom.qperm && n4k_ok(t, d, lbs, K)) {
     p.dec = Decomp::Fused4k;
     p.path = no_fk ? FoldPath::Rows : FoldPath::Ntt;
+  } else if (grouped && lfk::smp2_degree(d) && lbs == 1 && K <= 15 && ((b->planes[0] && b->planes[1]) || no_fk)) {
+    // d = 16 .. 512 (decompose_pow2.hip): only for a caller who opted in, with planes
+    // or without f_k buffers; with f_k and no planes the step stays Plain
+    p.dec = Decomp::FusedPow2;
+    p.path = no_fk ? FoldPath::Rows : FoldPath::Ntt;
   }
   return p;
 }
@@ -72,7 +78,7 @@ StepPlan step_plan(const lf_ajtai *aj, const lf_params *pr, int lbs, const Table
 // commit(z) from the decomposition's own rows. The decomposition is exact (f_coeff =
 // sum_k 2^(k lbs) D_k, or the step's error flag is raised) and the NTT is linear, so
 // A f = sum_k 2^(k lbs) A NTT(D_(1,k)): cm = sum_k 2^(k lbs) y_1[k]. A step that
-// commits z on the fused X^1024 + 1 / X^4096 + 1 decompositions therefore has side
+// commits z on the fused X^1024 + 1 / X^4096 + 1 / d = 16 .. 512 decompositions therefore has side
 // 1's plane 0 written as operand row 0, contracts it as vector 0 into y_1[0], and
 // fold_finish forms cm from the y_1[k] (y0_cm0's cm1_out). A function of (scheme,
 // params, buffers) alone, never context state: fold_commit, fold_dst and fold_finish
@@ -80,7 +86,7 @@ StepPlan step_plan(const lf_ajtai *aj, const lf_params *pr, int lbs, const Table
 // disagree.
 bool z_plane0(const lf_ajtai *aj, const lf_params *pr, int lbs, const Tables *t, const lf_fold_step_bufs *b) {
   const Decomp dec = step_plan(aj, pr, lbs, t, b).dec;
-  return dec == Decomp::Fused1024 || dec == Decomp::Fused4k;
+  return dec == Decomp::Fused1024 || dec == Decomp::Fused4k || dec == Decomp::FusedPow2;
 }
 int z_plane0(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, int lbs, const lf_fold_step_bufs *b, bool &z0) {
   Tables *t;
@@ -165,19 +171,20 @@ int fold_commit(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, int lb, int 
   const uint64_t *fc_side[2] = {b->acc_f_coeff, wi_f_coeff};
   const size_t kd = kappa * (size_t)d;
   // the fused decompositions write their digit planes straight into the MFMA operand
-  // buffer: X^1024 + 1 (kernels_n32.hip), Phi_72 (decompose_phi72.hip) and X^4096 + 1 (kernels_n4k.hip)
+  // buffer: X^1024 + 1 (kernels_n32.hip), Phi_72 (decompose_phi72.hip), X^4096 + 1 (kernels_n4k.hip)
+  // and d = 16 .. 512 (decompose_pow2.hip)
   StepPlan plan = step_plan(aj, pr, lbs, t, b);
   const bool fused = plan.dec == Decomp::Fused1024, fused24 = plan.dec == Decomp::Fused24,
-             fused4k = plan.dec == Decomp::Fused4k;
+             fused4k = plan.dec == Decomp::Fused4k, fusedp2 = plan.dec == Decomp::FusedPow2;
   // without f_k buffers the planes exist only as operand rows (step_sides), where
   // fold_finish reads f_0's inputs (k_fold_frag), or stay packed
   const bool no_fk = !b->fk[0] && !b->fk[1];
   // commit(z) rides as side 1's plane-0 row (row 0, extra = 1) instead of a row made from f
   const bool z0 = commit_f && z_plane0(aj, pr, lbs, t, b);
   if (b->planes[0] || b->planes[1]) {
-    if (!(fused24 || fused || fused4k) || lbs != 1 || !b->planes[0] || !b->planes[1])
+    if (!(fused24 || fused || fused4k || fusedp2) || lbs != 1 || !b->planes[0] || !b->planes[1])
       return fail(c, LF_ERR_INVALID_ARG,
-                  "packed planes: d = 24 or the fused d = 1024 / 4096 paths, b_small = 2, both sides");
+                  "packed planes: d = 24 or the fused d = 16 .. 512 / 1024 / 4096 paths, b_small = 2, both sides");
   }
   // X^1024 + 1 without f_k / f_coeff_k: the planes stay packed (the fused
   // decomposition's sign|magnitude words), f_0 comes from the coefficient-form
@@ -192,9 +199,10 @@ int fold_commit(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, int lb, int 
     if (b->fk_coeff[0] || b->fk_coeff[1])
       return fail(c, LF_ERR_INVALID_ARG, "Phi_72: f_k and f_coeff_k are both given or both NULL");
   } else if (no_fk) {
-    if (!fused && !fused4k)
-      return fail(c, LF_ERR_INVALID_ARG, "f_k buffers may be omitted only on the fused X^1024+1 / X^4096+1 paths");
-    if (fused4k && (b->fk_coeff[0] || b->fk_coeff[1]) && !(b->fk_coeff[0] && b->fk_coeff[1]))
+    if (!fused && !fused4k && !fusedp2)
+      return fail(c, LF_ERR_INVALID_ARG,
+                  "f_k buffers may be omitted only on the fused X^d+1 paths (d = 16 .. 512, 1024, 4096)");
+    if ((fused4k || fusedp2) && (b->fk_coeff[0] || b->fk_coeff[1]) && !(b->fk_coeff[0] && b->fk_coeff[1]))
       return fail(c, LF_ERR_INVALID_ARG, "f_coeff_k: both sides or neither");
     if (fused && !packed1024 && (!b->fk_coeff[0] || !b->fk_coeff[1]))
       return fail(c, LF_ERR_INVALID_ARG, "f_coeff_k: both sides or neither");
@@ -239,7 +247,7 @@ int fold_commit(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, int lb, int 
   // dead units: the planes' operand rows are left unwritten where a unit's plane is zero
   LF_TRY(grow_dead(c, (size_t)aj->geom.nch * 64));
   lfk::FusedSides sd{};
-  // without f_k, plane 0 of each side gets an operand row too (d = 1024 / 4096);
+  // without f_k, plane 0 of each side gets an operand row too (every X^d + 1 path);
   // z0: side 1's is row 0, with or without f_k, and row 0's dead units read as zero80
   const uint32_t rows = step_sides(sd, fc_side, b, extra, K, no_fk && !fused24, z0);
   sd.dead = c->dead;
@@ -249,6 +257,14 @@ int fold_commit(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, int lb, int 
     for (int s = 0; s < 2 && b->planes[0]; s++) sd.smg[s] = reinterpret_cast<uint32_t *>(b->planes[s]);
     PhaseTimer pt(c, LF_PHASE_DECOMPOSE);  // both sides in one launch
     LF_TRY(decompose_n4k_sides(c, t, sd, N, lb, L, K, c->frag, aj->geom.nch));
+  } else if (fusedp2) {
+    // the packed words go into the caller's planes when given, else the context's scratch
+    const size_t words = N * lfk::smp2_words(d);
+    if (!b->planes[0]) LF_TRY(grow(c, c->smg, c->smg_elems, 2 * words));
+    for (int s = 0; s < 2; s++)
+      sd.smg[s] = b->planes[0] ? reinterpret_cast<uint32_t *>(b->planes[s]) : c->smg + (size_t)s * words;
+    PhaseTimer pt(c, LF_PHASE_DECOMPOSE);  // both sides in one launch
+    LF_HIP(c, lfk::decompose_pow2(sd, N, d, lb, L, K, t->fwd, c->frag, aj->geom.nch, c->d_err, c->cur));
   } else if (fused) {
     // the packed words go straight into the caller's planes when given; fold_finish's
     // coefficient-form fold reads the digits from them
@@ -572,12 +588,15 @@ int lf_dev_expand_planes(lf_ctx *c, const lf_params *pr, const uint64_t *planes,
     LF_HIP(c, lfk::expand_phi72(reinterpret_cast<const uint2 *>(planes), lfk::mask24_elems(K, N), fck, fk, c->cur));
     return LF_OK;
   }
-  if ((d != 1024 && d != 4096) || K > 15) return fail(c, LF_ERR_UNSUPPORTED_RING, "packed planes: d = 24, 1024 or 4096");
+  if ((d != 1024 && d != 4096 && !lfk::smp2_degree(d)) || K > 15)
+    return fail(c, LF_ERR_UNSUPPORTED_RING, "packed planes: d = 24, 16 .. 512, 1024 or 4096");
   if (!fck && !fk) return LF_OK;
   // sign|magnitude words (d = 4096: the digit bytes) -> f_coeff_k, then f_k = NTT(f_coeff_k)
   // (CRT::elementwise_crt)
   uint64_t *dst = fck ? fck : fk;
-  if (d == 1024)
+  if (lfk::smp2_degree(d))
+    LF_HIP(c, lfk::expand_smp2(reinterpret_cast<const uint32_t *>(planes), N, d, K, dst, c->cur));
+  else if (d == 1024)
     LF_HIP(c, lfk::expand_sm(reinterpret_cast<const uint32_t *>(planes), N, K, dst, c->cur));
   else
     LF_HIP(c, lfk::expand_sm8(reinterpret_cast<const uint32_t *>(planes), N, K, dst, c->cur));
@@ -673,6 +692,16 @@ int lf_dev_fold_step_batch(lf_ctx *const *cs, int nsteps, const lf_ajtai *aj, co
     LF_TRY(fold_finish(cs[s], aj, pr, lb, lbs, W, bs[s], bs[s]->cm, z0[s]));
   }
   return LF_OK;
+}
+
+size_t lf_fold_step_planes_len(const lf_params *pr, size_t N) {
+  if (!pr || pr->b_small != 2 || pr->K < 1 || pr->K > 15) return 0;
+  const size_t K = pr->K, d = pr->d;
+  if (d == 24) return lfk::mask24_elems((int)K, N);
+  if (d == 1024) return N * lfk::SM1024_WORDS / 2;
+  if (d == 4096) return N * lfk::sm8_words((int)K) / 2;
+  if (lfk::smp2_degree((int)d)) return N * lfk::smp2_words((int)d) / 2;
+  return 0;  // d = 2048 and unsupported degrees: the step has no packed form
 }
 
 size_t lf_fold_step_partial_len(const lf_ajtai *aj, const lf_params *pr) {

@@ -2,7 +2,7 @@
 // one commented home of each layout. Writers (the pack kernels, from_w_ccs), readers
 // (the fused decompositions, the coefficient-form folds), the expanders
 // (lf_dev_expand_planes) and the host's buffer sizing all take the sizes, indices,
-// encode and decode from here. Three of the formats are public: callers keep them in
+// encode and decode from here. Four of the formats are public: callers keep them in
 // lf_fold_step_bufs.planes between steps (include/lf.h). Plain integer code that also
 // compiles for the host alone (tests/test_digit_pack.py runs it under the address and
 // UB sanitizers).
@@ -45,6 +45,23 @@ LF_HD size_t sm1024_word_of(size_t col, int j) { return sm1024_word(col, j >> 6,
 LF_HD int sm1024_half_of(int j) { return (j >> 5) & 1; }
 LF_HD int sm1024_digit(const uint32_t *words, size_t col, int j, int k) {
   return sm16_digit(words[sm1024_word_of(col, j)] >> (16 * sm1024_half_of(j)), k);
+}
+
+// ---------------------------------------------------------------- d = 2^k, 16 <= d <= 512: sm16 words (public)
+// d / 2 u32 per ring element, all K planes in one; one format for the six degrees.
+// Word j < d / 2 of element e sits at e d / 2 + j and holds
+// sm(x[j]) | sm(x[j + d / 2]) << 16: coefficient i is half i / (d / 2) of word
+// i mod (d / 2). A thread of the fused decomposition (decompose_pow2.hip) that owns
+// the coefficients i = t, t + T, .. of its element owns both halves of each of its
+// words, and neighbouring threads write neighbouring words.
+LF_HD bool smp2_degree(int d) { return d >= 16 && d <= 512 && (d & (d - 1)) == 0; }
+LF_HD size_t smp2_words(int d) { return (size_t)d / 2; }  // u32 per element
+LF_HD size_t smp2_word(size_t e, int d, int j) { return e * smp2_words(d) + (size_t)j; }
+LF_HD size_t smp2_word_of(size_t e, int d, int i) { return smp2_word(e, d, i & (d / 2 - 1)); }
+LF_HD int smp2_half_of(int d, int i) { return i >= d / 2 ? 1 : 0; }
+LF_HD uint32_t smp2_make(int64_t lo, int64_t hi) { return sign_mag16(lo) | sign_mag16(hi) << 16; }
+LF_HD int smp2_digit(const uint32_t *words, size_t e, int d, int i, int k) {
+  return sm16_digit(words[smp2_word_of(e, d, i)] >> (16 * smp2_half_of(d, i)), k);
 }
 
 // ---------------------------------------------------------------- d = 24: sm16 words (scratch)

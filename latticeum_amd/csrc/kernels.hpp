@@ -201,6 +201,17 @@ hipError_t fold_frag(const uint4 *frag, const FragGeom &g, const FoldRows &fr, c
 hipError_t decompose_fused(const FusedSides &sd, size_t N, int lb, int L, int K, const ring::NegaTables &fwd, uint4 *frag, int nch, int *err, uint64_t *sink, int ncu,
                            hipStream_t st);
 
+// ---------------------------------------------------------------- d = 2^k, 16 <= d <= 512, b_small = 2 (decompose_pow2.hip)
+// The fused decomposition of nside (<= 2) witnesses in one launch: the packed
+// sign|magnitude words (digitpack.hpp smp2_*) into sd.smg[s] (required), w_ccs_k, the
+// f_coeff_k / f_k rows where given, and the planes' operand rows (row0 / row_p0 of
+// sd, Lp = L order, offset form) straight into frag; sd.dead (may be null) gets the
+// flag of every (position, row) the launch owns. K <= 15, L <= 8.
+hipError_t decompose_pow2(const FusedSides &sd, size_t N, int d, int lb, int L, int K, const ring::NegaTables &fwd,
+                          uint4 *frag, int nch, int *err, hipStream_t st);
+// the packed words of N elements -> f_coeff_k [K][N][d] (digits mod p)
+hipError_t expand_smp2(const uint32_t *smg, size_t N, int d, int K, uint64_t *fck, hipStream_t st);
+
 // ---------------------------------------------------------------- coefficient-form fold, d = 1024 (fold_coeff.hip)
 // f_0 in coefficient form on the i8 matrix cores, X^1024 + 1, b_small = 2:
 // keys [ncol = nside N][K][64] u32 from decompose_fused's packed coefficients (smg);

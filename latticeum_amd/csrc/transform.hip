@@ -5,6 +5,7 @@
 // (kernels_n32.hip) and d = 4096 (kernels_n4k.hip) forms. The users of
 // ring::stockham4 share this one translation unit on purpose: compiled apart, the
 // transform kernels come out with different address arithmetic.
+// (decompose_pow2.hip instantiates stockham4 only for its own kernel, 16 elements per block.)
 // Data layout in HBM (every kernel file): AoS ring elements, d u64 each (d = 24 for
 // Phi_72 in the reference's in-place CRT layout [s0.c0, s0.c1, s0.c2, s1.c0, ..]
 // (stark-rings crt.rs:53-77), d = 2^k, 16 <= d <= 4096, for the negacyclic rings),

@@ -203,6 +203,52 @@ int lf_ajtai_d(const lf_ajtai *aj);
  * the AoS matrix given to lf_ajtai_create_device is then no longer read and may
  * be freed), 0 when commitments run on the VALU from the AoS matrix */
 int lf_ajtai_layout(const lf_ajtai *aj);
+/* bytes of device memory the scheme owns: its u64 matrix if it owns one (lf_ajtai_create, or a
+ * seeded scheme without the fragment form; a matrix borrowed through lf_ajtai_create_device
+ * is not counted), plus the fragment-order copy, plus the row-sum tables */
+size_t lf_ajtai_device_bytes(const lf_ajtai *aj);
+
+/* ---- A from a seed. A is a public parameter: every party derives the same matrix from
+ * seed[4], and a column shard derives only its own columns. The matrix is the kappa x
+ * ncols_total matrix of degree-d ring elements in NTT-slot form, canonical values (what
+ * lf_ajtai_create takes with LF_REPR_CANONICAL; for d = 24 an element is the 24 base-field
+ * words of its eight F_q^3 slots). Two derivations:
+ *
+ *  LF_AJTAI_SEED_POSEIDON2 (real parameters). Every seed[i] must be canonical (< p) and
+ *    kappa, ncols_total <= 2^32 (else LF_ERR_INVALID_ARG). For block j < d / 8 of element
+ *    (row, col), col the global column index, the 16-word state
+ *        s = (seed[0], seed[1], seed[2], seed[3], TAG, d, row, col, j, 0, 0, 0, 0, 0, 0, 0),
+ *        TAG = 0x4C46414A54414931
+ *    goes through the width-16 Poseidon2 permutation (the function and in/out convention of
+ *    lf_poseidon2_permute / lf_dev_poseidon2_permute), out = permute(s), and
+ *        A[row][col][8 j + i] = out[i]   for i < 8.
+ *    The outputs are canonical field elements: there is no rejection step.
+ *  LF_AJTAI_SEED_SPLITMIX (synthetic: what the tests and the benchmark call A). Word
+ *    ((row ncols_total + col) d + slot) of lf_dev_fill_uniform's stream for seed[0] over
+ *    kappa ncols_total d words; seed[1..3] must be 0 (else LF_ERR_INVALID_ARG).
+ *
+ * Every entry refuses an unsupported d with LF_ERR_UNSUPPORTED_RING and a zero size, an
+ * unknown kind, col0 + ncols > ncols_total or a matrix whose kappa ncols_total d 8 bytes
+ * do not fit 64 bits with LF_ERR_INVALID_ARG. */
+enum { LF_AJTAI_SEED_POSEIDON2 = 1, LF_AJTAI_SEED_SPLITMIX = 2 };
+/* the scheme over the columns [col0, col0 + ncols) of the seeded matrix (col0 = 0, ncols =
+ * ncols_total: all of it; a column shard passes its groups' range times L). To every entry
+ * that takes an lf_ajtai it is the scheme lf_ajtai_create makes from the expanded window:
+ * same geometry, same lf_ajtai_layout, bit-identical outputs. Where the scheme has the
+ * fragment form (lf_ajtai_layout 1) the generator writes the fragment order and the row-sum
+ * tables directly and no u64 matrix ever exists; creation's scratch does not grow with
+ * ncols. Where it has none, the u64 window is generated on the device and owned. */
+int lf_ajtai_create_seeded(lf_ctx *ctx, const uint64_t seed[4], int kind, size_t kappa, size_t ncols_total,
+                           size_t col0, size_t ncols, int d, lf_ajtai **out);
+/* host only, no context: the ncols d canonical words of row `row`, columns [col0, col0 + ncols) */
+int lf_ajtai_seeded_expand(const uint64_t seed[4], int kind, size_t kappa, size_t ncols_total, int d, size_t row,
+                           size_t col0, size_t ncols, uint64_t *out);
+/* the window rows [row0, row0 + nrows) x columns [col0, col0 + ncols) as u64 on the device,
+ * out_dev [nrows][ncols][d] (enqueued on the context's stream). out_dev must be 16-byte
+ * aligned (the words go out as 16-byte stores), else LF_ERR_INVALID_ARG */
+int lf_dev_ajtai_seeded_expand(lf_ctx *ctx, const uint64_t seed[4], int kind, size_t kappa, size_t ncols_total,
+                               int d, size_t row0, size_t nrows, size_t col0, size_t ncols, uint64_t *out_dev);
+
 /* commit_ntt: f has f_len NTT elements (must equal width), cm receives kappa */
 int lf_ajtai_commit(lf_ctx *ctx, const lf_ajtai *aj, const uint64_t *f, size_t f_len, uint64_t *cm,
                     int repr);

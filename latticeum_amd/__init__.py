@@ -23,6 +23,9 @@ P = (1 << 64) - (1 << 32) + 1
 REPR_CANONICAL = 0
 REPR_MONTGOMERY = 1
 SUPPORTED_D = (24, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096)
+# how an Ajtai matrix is derived from a seed (lf.h LF_AJTAI_SEED_*)
+AJTAI_SEED_POSEIDON2 = 1
+AJTAI_SEED_SPLITMIX = 2
 
 
 class LfError(RuntimeError):
@@ -302,6 +305,20 @@ class Context:
 
     def dev_fill_uniform(self, t, seed: int):
         self.check(self.lib.lf_dev_fill_uniform(self.h, _dptr(t), t.numel(), seed))
+
+    def dev_ajtai_seeded_expand(self, seed, kind: int, out, *, kappa: int, ncols_total: int, d: int,
+                                row0: int = 0, nrows: int | None = None, col0: int = 0, ncols: int | None = None):
+        """lf_dev_ajtai_seeded_expand: rows [row0, row0 + nrows) x columns [col0, col0 + ncols) of the
+        seeded matrix into the device tensor `out` [nrows][ncols][d]"""
+        nrows = kappa - row0 if nrows is None else nrows
+        ncols = ncols_total - col0 if ncols is None else ncols
+        if min(kappa, ncols_total, row0, nrows, col0, ncols, d) < 0:
+            raise ValueError("sizes and indices must not be negative (row0 past kappa, col0 past ncols_total?)")
+        if out.numel() != nrows * ncols * d:
+            raise ValueError("out must hold nrows * ncols * d words")
+        s = _seed4(seed)
+        self.check(self.lib.lf_dev_ajtai_seeded_expand(self.h, _ptr(s), kind, kappa, ncols_total, d, row0, nrows,
+                                                       col0, ncols, _dptr(out)))
 
     def dev_ajtai_commit(self, scheme: "AjtaiCommitmentScheme", vecs, cm):
         arr = (C.c_void_p * len(vecs))(*[_dptr(v) for v in vecs])
@@ -1114,6 +1131,33 @@ def witness_split_w() -> int:
     return load().lf_witness_split_w()
 
 
+def _seed4(seed) -> np.ndarray:
+    """a seed as four u64: an int is (seed, 0, 0, 0)"""
+    s = np.zeros(4, np.uint64)
+    v = np.atleast_1d(np.asarray(seed, dtype=np.uint64))
+    if v.size > 4:
+        raise ValueError("a seed is at most four u64")
+    s[:v.size] = v
+    return s
+
+
+def ajtai_seeded_expand(seed, kind: int = AJTAI_SEED_POSEIDON2, *, kappa: int, ncols_total: int, d: int,
+                        row: int | None = None, col0: int = 0, ncols: int | None = None) -> np.ndarray:
+    """lf_ajtai_seeded_expand (host only, needs no Context): columns [col0, col0 + ncols) of the
+    matrix derived from `seed`, canonical -- one row as [ncols, d], or every row as [kappa, ncols, d]"""
+    lib = load()
+    n = ncols_total - col0 if ncols is None else ncols
+    if min(kappa, ncols_total, col0, n, d) < 0 or (row is not None and row < 0):
+        raise ValueError("sizes and indices must not be negative (col0 past ncols_total?)")
+    s = _seed4(seed)
+    rows = range(kappa) if row is None else [row]
+    out = np.empty((len(rows), n, d), np.uint64)
+    for i, r in enumerate(rows):
+        _chk(lib.lf_ajtai_seeded_expand(_ptr(s), kind, kappa, ncols_total, d, r, col0, n, _ptr(out[i])),
+             "lf_ajtai_seeded_expand")
+    return out if row is None else out[0]
+
+
 class AjtaiCommitmentScheme:
     """latticefold commitment_scheme.rs:17-78 -- kappa x n Ajtai matrix (NTT form)."""
 
@@ -1135,6 +1179,28 @@ class AjtaiCommitmentScheme:
         self.layout = ctx.lib.lf_ajtai_layout(h)
         if self.layout == 1:
             self._keep = None
+
+    @classmethod
+    def seeded(cls, ctx: Context, seed, kind: int = AJTAI_SEED_POSEIDON2, *, kappa: int, ncols: int, d: int,
+               col0: int = 0, ncols_total: int | None = None) -> "AjtaiCommitmentScheme":
+        """lf_ajtai_create_seeded: the scheme over columns [col0, col0 + ncols) of the matrix
+        derived from `seed` (lf.h); with the fragment form no u64 matrix ever exists"""
+        self = cls.__new__(cls)
+        self.ctx, self.h, self._keep = ctx, None, None
+        h = C.c_void_p()
+        s = _seed4(seed)
+        ctx.check(ctx.lib.lf_ajtai_create_seeded(ctx.h, _ptr(s), kind, kappa, ncols if ncols_total is None
+                                                 else ncols_total, col0, ncols, d, C.byref(h)))
+        self.h = h
+        self.kappa, self.width, self.d = kappa, ncols, d
+        self.layout = ctx.lib.lf_ajtai_layout(h)
+        return self
+
+    @property
+    def device_bytes(self) -> int:
+        """lf_ajtai_device_bytes: device memory the scheme owns (its u64 matrix if owned, the
+        fragment-order copy, the row-sum tables)"""
+        return self.ctx.lib.lf_ajtai_device_bytes(self.h)
 
     def commit_ntt(self, f, repr: int = REPR_CANONICAL) -> np.ndarray:
         x = _u64(f)

@@ -114,6 +114,10 @@ SIGNATURES = {
     "lf_ajtai_width": (SZ, [VP]),
     "lf_ajtai_d": (I, [VP]),
     "lf_ajtai_layout": (I, [VP]),
+    "lf_ajtai_device_bytes": (SZ, [VP]),
+    "lf_ajtai_create_seeded": (I, [VP, VP, I, SZ, SZ, SZ, SZ, I, C.POINTER(VP)]),
+    "lf_ajtai_seeded_expand": (I, [VP, I, SZ, SZ, I, SZ, SZ, SZ, VP]),
+    "lf_dev_ajtai_seeded_expand": (I, [VP, VP, I, SZ, SZ, I, SZ, SZ, SZ, SZ, VP]),
     "lf_ajtai_commit": (I, [VP, VP, VP, SZ, VP, I]),
     "lf_witness_from_w_ccs": (I, [VP, C.POINTER(LfParams), VP, SZ, VP, VP, I]),
     "lf_witness_from_f": (I, [VP, C.POINTER(LfParams), VP, SZ, VP, VP, I]),

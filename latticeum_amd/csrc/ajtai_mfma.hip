@@ -89,16 +89,8 @@ FragGeom frag_geom(size_t ncols, int Lp) {
 // produced on the fly; dv = virtual slots per element (d, or 40 for PHI72).
 // ONEROW (a single operand row, the commit of one witness): the tile's 8 "rows"
 // are 8 consecutive chunks of that row instead, so no thread idles.
-constexpr int TF_S = 16, TF_R = 8, TF_J = 34;
-// virtual slots 16 SB .. 16 SB + 15 (those below 40) of one Phi_72 element
-template <int SB>
-__device__ __forceinline__ void phi72_evals(const uint64_t *e, uint64_t *ev) {
-#pragma unroll
-  for (int i = 0; i < TF_S; i++)
-    if (SB * TF_S + i < 40) ev[i] = ring::phi72_eval(e, SB * TF_S + i);
-}
-// qd > 0: operand slot of slot s is (s % 4) qd + s / 4 (FragGeom::qperm, qd = d / 4)
-__host__ __device__ __forceinline__ size_t op_slot(size_t s, int qd) { return qd ? (s & 3) * qd + (s >> 2) : s; }
+// (the tile's shape TF_S, TF_R, TF_J, phi72_evals and op_slot: frag.hpp, shared
+// with the writer that generates A from a seed, ajtai_seeded.hip)
 template <bool VMAJOR, bool PHI72, bool ONEROW>
 __global__ void __launch_bounds__(256) k_to_frag(VecPtrs rows, int rlo, int rhi, int d, int dv, int nch, int Lp,
                                                  size_t Wp, uint4 *frag, int qd) {

@@ -141,6 +141,20 @@ __device__ __forceinline__ size_t frag_column(int c, int t, int Lp, size_t Wp, b
   return g * Lp + l;
 }
 
+// The tile of the kernels that write operand rows in fragment order (k_to_frag,
+// ajtai_mfma.hip; k_seed_frag, ajtai_seeded.hip): 16 slots x 8 rows x 32 columns,
+// rows padded to 34 words.
+constexpr int TF_S = 16, TF_R = 8, TF_J = 34;
+// virtual slots 16 SB .. 16 SB + 15 (those below 40) of one Phi_72 element
+template <int SB>
+__device__ __forceinline__ void phi72_evals(const uint64_t *e, uint64_t *ev) {
+#pragma unroll
+  for (int i = 0; i < TF_S; i++)
+    if (SB * TF_S + i < 40) ev[i] = ring::phi72_eval(e, SB * TF_S + i);
+}
+// qd > 0: operand slot of slot s is (s % 4) qd + s / 4 (FragGeom::qperm, qd = d / 4)
+__host__ __device__ __forceinline__ size_t op_slot(size_t s, int qd) { return qd ? (s & 3) * qd + (s >> 2) : s; }
+
 // folding.rs:258-268 compute_f_0 from the D8 operand rows (the packed / f_k-free
 // steps' fallback for a rho that is not short, and d = 4096's fold): virtual block
 // vb < (d / 16) nch takes 16 slots (four slot quads, one 128-B line of every

@@ -155,6 +155,18 @@ hipError_t ajtai_mfma_steps(const uint4 *Af, const uint64_t *kr, size_t kappa, c
                             hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, const DeadUnits *dead = nullptr,
                             const uint4 *zero80 = nullptr, uint32_t *toptbl = nullptr);
 
+// ---------------------------------------------------------------- A from a seed (ajtai_seeded.hip)
+struct SeedGen;  // ajtai_seed.hpp
+// Af (mfma_ktiles(kappa) tiles) and kr (ajtai_rowsums_elems) of the columns col0 .. col0 + g's
+// width of the seeded matrix, as to_frag and ajtai_rowsums make them from the u64 matrix;
+// part: seeded_frag_scratch_elems() u64 of scratch, whose size does not depend on the width
+size_t seeded_frag_scratch_elems(size_t kappa, int d, const FragGeom &g);
+hipError_t seeded_to_frag(const SeedGen &sg, size_t kappa, size_t col0, const FragGeom &g, uint4 *Af, uint64_t *kr,
+                          uint64_t *part, hipStream_t st);
+// out [nrows][ncols][d] <- rows row0 .., columns col0 .. of the seeded matrix
+hipError_t seeded_expand(const SeedGen &sg, size_t row0, size_t nrows, size_t col0, size_t ncols, uint64_t *out,
+                         hipStream_t st);
+
 // ---------------------------------------------------------------- d = 1024 on the register-resident 32 x 32 NTT (kernels_n32.hip)
 // W below which from_w_ccs / from_f run one half-wave per (element, limb)
 size_t witness_split_w();

@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <memory>
 
+#include "ajtai_seed.hpp"
 #include "api_internal.hpp"
 
 // negacyclic twiddle tables for degree d (built on the host once per context)
@@ -592,6 +593,67 @@ int lf_ajtai_create_device(lf_ctx *c, const uint64_t *A_dev, size_t kappa, size_
   }
   *out = aj;
   return LF_OK;
+}
+
+// A from a seed (lf.h): with the fragment form the generator writes Af and kr
+// directly (ajtai_seeded.hip) and aj->A stays null -- nothing reads it on such a
+// scheme; without it the u64 window is generated, owned, and the scheme is what
+// lf_ajtai_create makes
+int lf_ajtai_create_seeded(lf_ctx *c, const uint64_t seed[4], int kind, size_t kappa, size_t ncols_total,
+                           size_t col0, size_t ncols, int d, lf_ajtai **out) {
+  DevGuard g(c);
+  if (!c || !out) return LF_ERR_INVALID_ARG;
+  const char *why;
+  const int rc0 = lfk::seed_check(seed, kind, kappa, ncols_total, d, col0, ncols, &why);
+  if (rc0 != LF_OK) return fail(c, rc0, why);
+  const lfk::SeedGen sg{{seed[0], seed[1], seed[2], seed[3]}, kind, d, ncols_total};
+  std::unique_ptr<lf_ajtai, void (*)(lf_ajtai *)> aj(new lf_ajtai, lf_ajtai_destroy);
+  aj->device = c->device;
+  aj->kappa = kappa;
+  aj->ncols = ncols;
+  aj->d = d;
+  if (use_mfma(d, kappa)) {
+    aj->geom = ajtai_geom(ncols);
+    aj->geom.qperm = d == 4096;
+    const size_t n = lfk::frag_elems(aj->geom, d);
+    LF_HIP(c, hipMalloc((void **)&aj->Af, n * lfk::mfma_ktiles(kappa) * sizeof(uint4)));
+    LF_HIP(c, hipMalloc((void **)&aj->kr, lfk::ajtai_rowsums_elems(kappa, d, aj->geom.Lp) * sizeof(uint64_t)));
+    DevBuf part;
+    LF_TRY(dev_alloc(c, part, lfk::seeded_frag_scratch_elems(kappa, d, aj->geom)));
+    LF_HIP(c, lfk::seeded_to_frag(sg, kappa, col0, aj->geom, aj->Af, aj->kr, part.p, c->cur));
+    LF_HIP(c, hipStreamSynchronize(c->cur));
+  } else {
+    uint64_t *A = nullptr;
+    LF_HIP(c, hipMalloc((void **)&A, kappa * ncols * (size_t)d * sizeof(uint64_t)));
+    aj->A = A;
+    aj->owned = true;
+    LF_HIP(c, lfk::seeded_expand(sg, 0, kappa, col0, ncols, A, c->cur));
+    LF_HIP(c, hipStreamSynchronize(c->cur));
+  }
+  *out = aj.release();
+  return LF_OK;
+}
+
+int lf_dev_ajtai_seeded_expand(lf_ctx *c, const uint64_t seed[4], int kind, size_t kappa, size_t ncols_total, int d,
+                               size_t row0, size_t nrows, size_t col0, size_t ncols, uint64_t *out_dev) {
+  DevGuard g(c);
+  if (!c || !out_dev) return LF_ERR_INVALID_ARG;
+  const char *why;
+  const int rc0 = lfk::seed_check(seed, kind, kappa, ncols_total, d, col0, ncols, &why);
+  if (rc0 != LF_OK) return fail(c, rc0, why);
+  if (!nrows || row0 > kappa || nrows > kappa - row0) return fail(c, LF_ERR_INVALID_ARG, "row0 + nrows exceeds kappa");
+  if ((uintptr_t)out_dev % 16) return fail(c, LF_ERR_INVALID_ARG, "out_dev must be 16-byte aligned");
+  const lfk::SeedGen sg{{seed[0], seed[1], seed[2], seed[3]}, kind, d, ncols_total};
+  LF_HIP(c, lfk::seeded_expand(sg, row0, nrows, col0, ncols, out_dev, c->cur));
+  return LF_OK;
+}
+
+size_t lf_ajtai_device_bytes(const lf_ajtai *aj) {
+  if (!aj) return 0;
+  size_t b = aj->owned && aj->A ? aj->kappa * aj->ncols * (size_t)aj->d * sizeof(uint64_t) : 0;
+  if (aj->Af) b += lfk::frag_elems(aj->geom, aj->d) * lfk::mfma_ktiles(aj->kappa) * sizeof(uint4);
+  if (aj->kr) b += lfk::ajtai_rowsums_elems(aj->kappa, aj->d, aj->geom.Lp) * sizeof(uint64_t);
+  return b;
 }
 
 void lf_ajtai_destroy(lf_ajtai *aj) {

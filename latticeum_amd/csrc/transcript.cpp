@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/lf.h"
+#include "ajtai_seed.hpp"
 #include "gl.hpp"
 #include "ring.hpp"
 #if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
@@ -582,6 +583,32 @@ int lf_merkle_verify(const uint64_t root[4], const uint64_t *row, size_t width, 
   }
   for (int w = 0; w < 4; w++)
     if (s[w] != gl::canon(root[w])) return LF_ERR_VERIFICATION;
+  return LF_OK;
+}
+
+// one row's window of the seeded Ajtai matrix (lf.h, ajtai_seed.hpp), on the host:
+// what a party without the device derives, and what pins the device generators
+int lf_ajtai_seeded_expand(const uint64_t seed[4], int kind, size_t kappa, size_t ncols_total, int d, size_t row,
+                           size_t col0, size_t ncols, uint64_t *out) {
+  const char *why;
+  const int rc = lfk::seed_check(seed, kind, kappa, ncols_total, d, col0, ncols, &why);
+  if (rc != LF_OK) return rc;
+  if (!out || row >= kappa) return LF_ERR_INVALID_ARG;
+  const lfk::SeedGen g{{seed[0], seed[1], seed[2], seed[3]}, kind, d, ncols_total};
+  for (size_t c = 0; c < ncols; c++) {
+    uint64_t *e = out + c * (size_t)d;
+    if (kind == LF_AJTAI_SEED_POSEIDON2) {
+      for (int j = 0; j < d / 8; j++) {
+        uint64_t s[16];
+        lfk::seed_p2_state(g, row, col0 + c, j, s);
+        permute(s);
+        memcpy(e + 8 * j, s, 8 * sizeof(uint64_t));
+      }
+    } else {
+      const uint64_t base = ((uint64_t)row * ncols_total + col0 + c) * (uint64_t)d;
+      for (int i = 0; i < d; i++) e[i] = lfk::seed_splitmix_word(seed[0], base + (uint64_t)i);
+    }
+  }
   return LF_OK;
 }
 

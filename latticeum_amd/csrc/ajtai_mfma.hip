@@ -60,6 +60,8 @@
 // matrix.rs:168-178 does).
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
+#include <utility>
 
 #include "frag.hpp"
 #include "kernels.hpp"
@@ -293,13 +295,16 @@ __device__ __forceinline__ void lgkm_wait_digit(int kb) {
     default: asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); break;
   }
 }
-template <int CPOL>
-__device__ __forceinline__ v4i gload16(const v4i *p) {
+// 16 bytes at base + voff + OFF: a wave-uniform base in scalar registers, the
+// lane's 32-bit byte offset, and the instruction's immediate (12 bits)
+template <int CPOL, int OFF>
+__device__ __forceinline__ v4i gload16(const void *base, uint32_t voff) {
+  static_assert(OFF >= 0 && OFF < 4096, "immediate offset");
   v4i r;
   if (CPOL == 2)
-    asm volatile("global_load_dwordx4 %0, %1, off nt" : "=v"(r) : "v"(p) : "memory");
+    asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3 nt" : "=v"(r) : "v"(voff), "s"(base), "n"(OFF) : "memory");
   else
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(r) : "v"(p) : "memory");
+    asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(r) : "v"(voff), "s"(base), "n"(OFF) : "memory");
   return r;
 }
 // Several independent fold steps against the same A (nsteps > 1, StepOps): the
@@ -316,6 +321,16 @@ __device__ __forceinline__ v4i gload16(const v4i *p) {
 // rows, its dead bit that step's flag of that row, and output column v goes to
 // step_v's plane, row row_v. Those are wave-uniform per piece, resolved once
 // here into scalar registers; the chunk loop is the same code.
+// f(integral_constant<int, 0>) .. f(integral_constant<int, N - 1>): an unrolled
+// loop whose index is a compile-time constant (asm immediates)
+template <class F, int... I>
+__device__ __forceinline__ void static_for_seq(F &&f, std::integer_sequence<int, I...>) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void static_for(F &&f) {
+  static_for_seq(f, std::make_integer_sequence<int, N>{});
+}
 template <class T>
 __device__ __forceinline__ T *uniform_ptr(T *p) {
   const uint64_t x = (uint64_t)(uintptr_t)p;
@@ -330,7 +345,10 @@ __global__ void __launch_bounds__(256, 1) k_ajtai_mfma_ra(const uint4 *Af, const
                                                          const uint32_t *tbl) {
   static_assert(DP >= 3 && DP <= 5, "F buffers: DP x 32 KiB of LDS");
   __shared__ uint4 Fl[DP][32 * 64];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
+  // the wave index on the scalar side: the slot, the split, the operand bases and
+  // every copy's LDS destination (m0) derive from it by scalar arithmetic
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int per = 8 * ktiles * nsteps;
   const int grp = blockIdx.x / per, rem = blockIdx.x - grp * per;
   const int stp = rem / (8 * ktiles), rem2 = rem - stp * 8 * ktiles;
@@ -351,14 +369,20 @@ __global__ void __launch_bounds__(256, 1) k_ajtai_mfma_ra(const uint4 *Af, const
   v16i acc[15];
 #pragma unroll
   for (int t = 0; t < 15; t++) acc[t] = (v16i){0};
-  const v4i *pa = reinterpret_cast<const v4i *>(Af + kt * tile_u4 + ((size_t)s * nch * 8) * 64 + lane);
+  // A: the slot's tiles from a scalar base; lane l of digit k reads the bytes at
+  // 1024 k + 16 l of the chunk's 8 KiB, as the lane's offset (16 l, or 4096 + 16 l
+  // for the digits from 4 on) plus the load's immediate
+  const uint4 *pa = Af + kt * tile_u4 + ((size_t)s * nch * 8) * 64;
+  const uint32_t va0 = 16u * lane, va1 = va0 + 4096u;
   const uint4 *ft = Ff + (size_t)(s >> 2) * nch * FV_CHUNK;
   v4i ra[DP][8];
-  auto load_a = [&](int c, v4i *dstr) {
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-      dstr[k] = gload16<CPA>(pa + ((size_t)c * 8 + k) * 64);
-    }
+  auto load_a_k = [&](int c, auto k_) __attribute__((always_inline)) -> v4i {
+    constexpr int k = decltype(k_)::value;
+    const uint4 *cb = pa + (size_t)c * 8 * 64;
+    return gload16<CPA, (k & 3) * 1024>(cb, k < 4 ? va0 : va1);
+  };
+  auto load_a = [&](int c, v4i *dstr) __attribute__((always_inline)) {
+    static_for<8>([&](auto k_) __attribute__((always_inline)) { dstr[decltype(k_)::value] = load_a_k(c, k_); });
   };
   const int nrow = TOP ? nent : nvec;  // rows of the tile
   const int nf = __builtin_amdgcn_readfirstlane((nrow - w + 3) >> 2 < 8 ? (nrow - w + 3) >> 2 : 8);  // wave-uniform
@@ -368,14 +392,19 @@ __global__ void __launch_bounds__(256, 1) k_ajtai_mfma_ra(const uint4 *Af, const
   // into StepOps would send the struct to scratch). Entries are clamped
   // (top_step, top_row), so a wrong table cannot form an address outside the
   // launch's buffers.
+  // (each piece's flags go into the dead masks dm[], described below, as the
+  // piece is resolved: eight flag pointers kept for a later pass cost the top
+  // class 16 scalar registers it does not have)
+  constexpr int NDM = (AJ_CPS + 63) / 64;
+  uint32_t dm[NDM];
+#pragma unroll
+  for (int m = 0; m < NDM; m++) dm[m] = 0;
   const uint4 *ftq[8];
-  const uint8_t *flq[8];
   if (TOP) {
-    const int wu = __builtin_amdgcn_readfirstlane(w);
-    const size_t quad = (size_t)__builtin_amdgcn_readfirstlane(s >> 2) * nch * FV_CHUNK;
+    const size_t quad = (size_t)(s >> 2) * nch * FV_CHUNK;
 #pragma unroll
     for (int q = 0; q < 8; q++) {
-      const uint32_t e = __builtin_amdgcn_readfirstlane(tbl[1 + 32 * stp + 4 * q + wu]);
+      const uint32_t e = __builtin_amdgcn_readfirstlane(tbl[1 + 32 * stp + 4 * q + w]);
       const int est = top_step(e, nsteps), er = top_row(e);
       const uint4 *f = so_.Ff[0];
       DeadUnits du = so_.dead[0];
@@ -386,7 +415,15 @@ __global__ void __launch_bounds__(256, 1) k_ajtai_mfma_ra(const uint4 *Af, const
         du.rows = est == k ? so_.dead[k].rows : du.rows;
       }
       ftq[q] = uniform_ptr(f + quad + (size_t)er * 64);
-      flq[q] = uniform_ptr(du.flags && ((du.rows >> er) & 1u) ? du.flags + er : (const uint8_t *)nullptr);
+      const uint8_t *fl = uniform_ptr(du.flags && ((du.rows >> er) & 1u) ? du.flags + er : (const uint8_t *)nullptr);
+      if (q < nf && fl) {  // uniform
+#pragma unroll
+        for (int m = 0; m < NDM; m++) {
+          const int c = c0 + lane + 64 * m;
+          if (c < c1)
+            dm[m] |= ((uint32_t)(fl[(size_t)c * 64] & 1u) << (2 * q)) | ((uint32_t)(fl[(size_t)c * 64 + 32] & 1u) << (2 * q + 1));
+        }
+      }
     }
   }
   // Dead units (DeadUnits: pieces the decomposition did not write, zero): lane l
@@ -397,27 +434,9 @@ __global__ void __launch_bounds__(256, 1) k_ajtai_mfma_ra(const uint4 *Af, const
   // counts hold); HBM reads of dead units are gone, and the products on them go
   // with the top class, whose tiles leave out the rows that are dead on every
   // top-limb unit. Read here, before any operand copy is in flight.
-  constexpr int NDM = (AJ_CPS + 63) / 64;
   const DeadUnits du = so_.dead[TOP ? 0 : stp];
   const bool has_dead = TOP || (du.flags != nullptr && du.rows != 0);  // uniform
-  uint32_t dm[NDM];
-#pragma unroll
-  for (int m = 0; m < NDM; m++) dm[m] = 0;
-  if (TOP) {
-#pragma unroll
-    for (int m = 0; m < NDM; m++) {
-      const int c = c0 + lane + 64 * m;
-      if (c < c1) {
-        uint32_t bits = 0;
-#pragma unroll
-        for (int q = 0; q < 8; q++)
-          if (q < nf && flq[q])  // uniform
-            bits |= ((uint32_t)(flq[q][(size_t)c * 64] & 1u) << (2 * q)) |
-                    ((uint32_t)(flq[q][(size_t)c * 64 + 32] & 1u) << (2 * q + 1));
-        dm[m] = bits;
-      }
-    }
-  } else if (has_dead) {
+  if (!TOP && has_dead) {
 #pragma unroll
     for (int m = 0; m < NDM; m++) {
       const int c = c0 + lane + 64 * m;
@@ -435,12 +454,18 @@ __global__ void __launch_bounds__(256, 1) k_ajtai_mfma_ra(const uint4 *Af, const
       }
     }
   }
+  // Every flag load has landed before the first operand copy is issued (the
+  // first copy's dead mask needs them anyway). Said to the compiler as a wait of
+  // its own: the row tests above are scalar branches, so a loaded word may go
+  // unused, and the compiler, which cannot see the asm loads below, would wait
+  // for that word's register with a full vmcnt(0) inside the chunk loop.
+  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
   // c uniform. Each dm[m] is read with its own readlane and the word picked on
   // the scalar side: a per-lane select over dm[] made the compiler keep the
   // array in LDS, and that read's lgkmcnt(0) wait drained the chunk's 8 operand
   // reads before its first product.
+  // (without dead units dm[] is zero, so no branch on has_dead is needed)
   auto dead_mask = [&](int c) -> uint32_t {
-    if (!has_dead) return 0u;
     const int ci = c - c0, m = ci >> 6, l = ci & 63;
     uint32_t r = __builtin_amdgcn_readlane(dm[0], l);
 #pragma unroll
@@ -452,26 +477,40 @@ __global__ void __launch_bounds__(256, 1) k_ajtai_mfma_ra(const uint4 *Af, const
   };
   const int hl = lane >> 5;
   const uint4 *z80 = so_.zero80 + (lane & 31);
-  // (the source is selected as a uint4 pointer in place: a pointer handed to the
-  // builtin through a lambda's return value makes clang drop the host-side kernel stub)
-  auto stage_f = [&](int c, int buf) {
-    const uint32_t dmask = dead_mask(c);
-#pragma unroll
-    for (int q = 0; q < 8; q++) {
-      const int j = 4 * q + w;
-      // TOP: the same expression with the piece's own rows for ft + j 64 (the swizzle stays on the tile row j)
-      const uint4 *live = TOP ? ftq[q] + (size_t)c * FV_CHUNK + fl_pi(j, lane)
-                              : ft + (size_t)c * FV_CHUNK + j * 64 + fl_pi(j, lane);
-      const uint4 *src = ((dmask >> (2 * q + hl)) & 1u) ? z80 : live;
-      if (q < nf) __builtin_amdgcn_global_load_lds((const void *)src, (lds_void *)&Fl[buf][j * 64], 16, 0, CPF);
-    }
-  };
-  auto stage_f_piece = [&](int c, int buf, int q, uint32_t dmask) {
+  // Piece q of chunk c: tile row j = 4 q + w, lane l from the 16 bytes at
+  // fl_pi(j, l) of the row's KiB. Only the swizzle (two values per lane: it
+  // depends on j & 7 = 4 (q & 1) + w), the half hl and the dead select are per
+  // lane; the row's address and the LDS destination (m0) are scalar sums.
+  const uint32_t pi0 = 16u * fl_pi(w, lane), pi1 = 16u * fl_pi(4 + w, lane);
+  const uint32_t lw0 = (uint32_t)(uintptr_t)&Fl[0][0] + 1024u * w;  // LDS address of tile row w, buffer 0
+  auto stage_f_piece = [&](int c, int buf, int q, uint32_t dmv) __attribute__((always_inline)) {
     const int j = 4 * q + w;
-    const uint4 *live = TOP ? ftq[q] + (size_t)c * FV_CHUNK + fl_pi(j, lane)
-                            : ft + (size_t)c * FV_CHUNK + j * 64 + fl_pi(j, lane);
-    const uint4 *src = ((dmask >> (2 * q + hl)) & 1u) ? z80 : live;
-    __builtin_amdgcn_global_load_lds((const void *)src, (lds_void *)&Fl[buf][j * 64], 16, 0, CPF);
+    // TOP: the piece's own rows for ft + j 64 (the swizzle stays on the tile row j)
+    const uint4 *row = TOP ? ftq[q] + (size_t)c * FV_CHUNK : ft + (size_t)c * FV_CHUNK + j * 64;
+    const uint4 *live = reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(row) + ((q & 1) ? pi1 : pi0));
+    const uint4 *src = (dmv & (1u << (2 * q))) ? z80 : live;
+    // m0 = the wave's first row of buffer 0 + 32 KiB buf + 4 KiB q, one scalar add
+    // (as 8 DP destinations kept in scalar registers the top class runs out of them).
+    // m0 is reserved, so it cannot be named as a clobber; nothing else in this
+    // kernel reads it (no other LDS-DMA, no ds_ op that takes m0 on gfx950).
+    if (CPF == 2)
+      asm volatile("s_add_i32 m0, %1, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off nt"
+                   :: "v"(src), "s"(lw0), "i"((buf * 32 + 4 * q) * 1024) : "memory", "scc");
+    else
+      asm volatile("s_add_i32 m0, %1, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off"
+                   :: "v"(src), "s"(lw0), "i"((buf * 32 + 4 * q) * 1024) : "memory", "scc");
+  };
+  // this lane's view of a chunk's dead mask: bit 2 q is its half of piece q
+  auto lane_mask = [&](uint32_t dmask) -> uint32_t {
+    uint32_t v = dmask >> hl;
+    asm volatile("" : "+v"(v));  // (one shift per chunk, not a lane-side mask per piece)
+    return v;
+  };
+  auto stage_f = [&](int c, int buf) __attribute__((always_inline)) {
+    const uint32_t dmv = lane_mask(dead_mask(c));
+#pragma unroll
+    for (int q = 0; q < 8; q++)
+      if (q < nf) stage_f_piece(c, buf, q, dmv);
   };
   const int rh = 2 * (lane & 31) + (lane >> 5), fj = rh >> 1;
   int fpos[8];
@@ -482,28 +521,47 @@ __global__ void __launch_bounds__(256, 1) k_ajtai_mfma_ra(const uint4 *Af, const
     if (c0 + j < c1) load_a(c0 + j, ra[j]);
     if (j < DP - 1 && c0 + j < c1) stage_f(c0 + j, j);
   }
-  for (int cb = c0; cb < c1; cb += DP) {
+  // One round = DP chunks, chunk cb + j in F buffer j and A registers ra[j].
+  // STEADY: every chunk of the round has c + DP < c1, so F(c + DP - 1) and
+  // A(c + DP) exist and nothing is tested per copy or per load. NFC: the wave's
+  // piece count as a compile-time fact (-1: read nf). The tail form (STEADY
+  // false, NFC -1) tests per copy what the single loop tested. Either form
+  // reads exactly the addresses and writes exactly the LDS bytes that the single
+  // loop did, in the same order: a copy is issued iff c + DP - 1 < c1 and
+  // kb < nf, a load iff c + DP < c1, from the same expressions (zero80 only
+  // under a set dead bit), so vm_wait_chunk's counts hold in both.
+  auto round = [&](auto steady_, auto nfc_, int cb) __attribute__((always_inline)) {
+    constexpr bool STEADY = decltype(steady_)::value;
+    constexpr int NFC = decltype(nfc_)::value;
+    const int nfr = NFC >= 0 ? NFC : nf;
 #pragma unroll
     for (int j = 0; j < DP; j++) {
       const int c = cb + j;
-      if (c >= c1) continue;  // uniform (only in a split's last round)
-      if (c + DP - 1 < c1)
-        vm_wait_chunk<DP>(nf);
+      if (!STEADY && c >= c1) continue;  // uniform (only in a split's last round)
+      if (STEADY || c + DP - 1 < c1)
+        vm_wait_chunk<DP>(nfr);
       else
         vm_wait<0>();
       __builtin_amdgcn_s_barrier();  // every wave's F(c) landed; every wave is done reading F(c - 1)
       v4i b[8];
-      const uint32_t fbase = (uint32_t)(uintptr_t)&Fl[j][0];
+      // buffer j: 65536 (j >> 1) in the address, 32768 (j & 1) as the read's immediate (16 bits)
+      const uint32_t fbase = (uint32_t)(uintptr_t)&Fl[j & ~1][0];
       // the copies ride between the products instead of in front of them: F(c)
       // is read right after the barrier and each digit's 8 products wait only
       // for that digit; F(c + DP - 1)'s pieces follow the digit groups, and
       // A(c + DP)'s loads follow the last product reading that register
       // (the issue order F then A is unchanged, so vm_wait_chunk still holds)
 #pragma unroll
-      for (int k = 0; k < 8; k++) asm volatile("ds_read_b128 %0, %1" : "=v"(b[k]) : "v"(fbase + 16u * fpos[k]));
-      const bool more_f = c + DP - 1 < c1, more_a = c + DP < c1;
+      for (int k = 0; k < 8; k++) {
+        if (j & 1)
+          asm volatile("ds_read_b128 %0, %1 offset:32768" : "=v"(b[k]) : "v"(fbase + 16u * fpos[k]));
+        else
+          asm volatile("ds_read_b128 %0, %1" : "=v"(b[k]) : "v"(fbase + 16u * fpos[k]));
+      }
+      const bool more_f = STEADY || c + DP - 1 < c1, more_a = STEADY || c + DP < c1;
       const int fb = (j + DP - 1) % DP;
-      const uint32_t dmn = more_f ? dead_mask(c + DP - 1) : 0u;
+      const uint32_t dmn = more_f ? lane_mask(dead_mask(c + DP - 1)) : 0u;
+      const int ncopy = more_f ? nfr : 0;  // pieces of F(c + DP - 1) to issue
 #pragma unroll
       for (int kb = 0; kb < 8; kb++) {
         lgkm_wait_digit(kb);
@@ -517,22 +575,40 @@ __global__ void __launch_bounds__(256, 1) k_ajtai_mfma_ra(const uint4 *Af, const
           for (int ka = 0; ka < 8; ka++)
             acc[ka + kb] = __builtin_amdgcn_mfma_i32_32x32x32_i8(ra[j][ka], b[kb], acc[ka + kb], 0, 0, 0);
           __builtin_amdgcn_sched_barrier(0);
-          if (more_f && kb < nf) stage_f_piece(c + DP - 1, fb, kb, dmn);
+          if (kb < ncopy) stage_f_piece(c + DP - 1, fb, kb, dmn);
           __builtin_amdgcn_sched_barrier(0);
         } else {
-          if (more_f && nf == 8) stage_f_piece(c + DP - 1, fb, 7, dmn);
+          if (ncopy == 8) stage_f_piece(c + DP - 1, fb, 7, dmn);
           __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int ka = 0; ka < 8; ka++) {
+          static_for<8>([&](auto ka_) __attribute__((always_inline)) {
+            constexpr int ka = decltype(ka_)::value;
             acc[ka + 7] = __builtin_amdgcn_mfma_i32_32x32x32_i8(ra[j][ka], b[7], acc[ka + 7], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
-            if (more_a) ra[j][ka] = gload16<CPA>(pa + ((size_t)(c + DP) * 8 + ka) * 64);
+            if (more_a) ra[j][ka] = load_a_k(c + DP, ka_);
             __builtin_amdgcn_sched_barrier(0);
-          }
+          });
         }
       }
     }
-  }
+  };
+  // Steady state and tail as two loops. A round is steady while its last chunk
+  // has c + DP < c1; the rounds left, at most two, run the tail form. The
+  // steady loop is selected once by the wave's piece count: the step's counts
+  // (a full tile: 8; nvec = 29: 8, 7, 7, 7) have forms of their own, the rare
+  // ones run the tail form, which is the generic one, throughout. The 4 waves
+  // of a block run the same chunks whatever their forms, so the barriers pair up.
+  // The two steady loops stand in sequence behind flags the compiler cannot
+  // relate (as the arms of an if / else the register allocator copied the A
+  // registers between them and spilled).
+  using steady_t = std::integral_constant<bool, true>;
+  using tail_t = std::integral_constant<bool, false>;
+  int cb = c0;
+  int is8 = nf == 8, is7 = nf == 7;
+  asm volatile("" : "+v"(is8), "+v"(is7));
+  is8 = __builtin_amdgcn_readfirstlane(is8), is7 = __builtin_amdgcn_readfirstlane(is7);
+  for (; is8 && cb + 2 * DP - 1 < c1; cb += DP) round(steady_t{}, std::integral_constant<int, 8>{}, cb);
+  for (; is7 && cb + 2 * DP - 1 < c1; cb += DP) round(steady_t{}, std::integral_constant<int, 7>{}, cb);
+  for (; cb < c1; cb += DP) round(tail_t{}, std::integral_constant<int, -1>{}, cb);
   const int so = qd ? (s % qd) * 4 + s / qd : s;
   if (TOP) {
     // column v of the tile -> its entry's row of its step's plane pl0 + js

@@ -43,6 +43,13 @@
  *       zkvm/src/main.rs:231-234 (serialized_size); the LCCCS layout (lf_lcccs_(de)serialize)
  *       is this project's own (the reference serialises no LCCCS)
  *   zkvm/src/zk_latticefold.rs:37-102 zk_latticefold_prove (fold())  -> lf_fold_prove
+ *       (lf_prover_create, or lf_prover_create_lean: the decomposed witnesses as packed
+ *       digit planes only)
+ *   latticefold/src/arith.rs:273-297 Witness::get_fhat of the decomposed witnesses, as
+ *       its consumers read it (evaluate_mles, prepare_g1_and_3_k_mles_list, the folding
+ *       sumcheck) from the packed planes                          -> lf_dev_fhat_evaluate_planes,
+ *                                                                 lf_dev_fhat_lincomb_planes,
+ *                                                                 lf_sumcheck_prove_fold_planes
  *   zkvm/src/main.rs:305-344 initialize_accumulator's linearization  -> lf_linearize
  *   zkvm/src/zk_latticefold.rs:111-148 generate_verification_witness_vars -> lf_fold_replay
  *   latticefold/src/arith.rs:78-105 CCS::check_relation            -> lf_dev_ccs_check_relation
@@ -554,6 +561,16 @@ int lf_sumcheck_prove_ptrs(lf_ctx *ctx, lf_transcript *t, const lf_comb *comb, c
 int lf_sumcheck_prove_fold_digits(lf_ctx *ctx, lf_transcript *t, const lf_comb *comb, const uint64_t *mles5,
                                   const uint64_t *fc0, const uint64_t *fc1, int K, size_t N, size_t wstride, int nv,
                                   int d, uint64_t *work, uint64_t *proof, uint64_t *randomness);
+/* the same prover with the 2K decomposed witnesses given as the two sides' packed digit
+ * planes (lf_fold_step_bufs.planes[0] and [1] of N elements, exactly as the step writes
+ * them; K = pr->K): the proof and randomness of lf_sumcheck_prove_fold_digits over
+ * lf_dev_expand_planes's f_coeff_k of each side. LF_ERR_UNSUPPORTED_RING where
+ * lf_fold_step_planes_len(pr, 1) is 0 (d = 2048, b_small != 2, K > 15);
+ * LF_ERR_INVALID_ARG for a NULL pointer, N > 2^nv, or a comb that is not the folding
+ * kind with nk = 2K, B_SMALL = 2 */
+int lf_sumcheck_prove_fold_planes(lf_ctx *ctx, lf_transcript *t, const lf_comb *comb, const uint64_t *mles5,
+                                  const lf_params *pr, const uint64_t *planes0, const uint64_t *planes1, size_t N,
+                                  int nv, uint64_t *work, uint64_t *proof, uint64_t *randomness);
 /* the linearization sumcheck (LFLinearizationProver::prove's, linearization.rs:153-197
  * over linearization/utils.rs:63-104) with eq(beta) given by beta itself: the proof and
  * randomness of lf_sumcheck_prove over [mles..., eq(beta)] (same transcript), with
@@ -893,6 +910,19 @@ enum {
  * `enable` and the sums are cleared */
 int lf_prover_timing(lf_prover *prover, int enable, double *span_ms);
 int lf_prover_create(lf_ctx *ctx, const lf_ajtai *aj, const lf_params *pr, const lf_ccs *ccs, lf_prover **out);
+/* A prover whose 2K decomposed witnesses live only as packed digit planes
+ * (lf_fold_step_planes_len u64 per side) beside one N-element scratch, instead of the
+ * 4 K N d u64 of f_k / f_coeff_k rows: lf_fold_prove decomposes into the planes and every
+ * f_hat reader (v_s, g1 / g3, the folding sumcheck's first round, theta_s) reads them
+ * (lf_dev_fhat_evaluate_planes, lf_dev_fhat_lincomb_planes, lf_sumcheck_prove_fold_planes).
+ * The same proofs, instances and witnesses, bit for bit, as lf_prover_create's prover, and
+ * every call that takes a prover works on it. LF_ERR_INVALID_ARG (lf_ctx_last_error names
+ * the reason) where the step has no packed form for this (scheme, params): a scheme
+ * without fragments or not grouped by this L, b_small != 2, K > 15, d = 2048. */
+int lf_prover_create_lean(lf_ctx *ctx, const lf_ajtai *aj, const lf_params *pr, const lf_ccs *ccs, lf_prover **out);
+int lf_prover_is_lean(const lf_prover *prover); /* 1: made by lf_prover_create_lean; else (or NULL) 0 */
+/* bytes of the prover's carved device allocation (either kind of prover; 0 for NULL) */
+size_t lf_prover_device_bytes(const lf_prover *prover);
 void lf_prover_destroy(lf_prover *prover);
 const char *lf_prover_last_error(const lf_prover *prover);
 /* LFLinearizationProver::prove of a CCCS (cm, x_ccs) with witness w on a fresh
@@ -950,6 +980,19 @@ int lf_dev_mle_lincomb(lf_ctx *ctx, int d, const uint64_t *mles, size_t stride, 
  * witnesses read from their digit coefficient rows (every value 0, 1 or -1; wstride u64 apart,
  * 0 = N d; zero past N <= 2^nv); coef: nw tau NTT elements on the device */
 int lf_dev_fhat_lincomb_digits(lf_ctx *ctx, int d, const uint64_t *f_coeff, size_t N, size_t wstride, int nw, int nv,
+                               const uint64_t *coef, uint64_t *io);
+/* The f_hat MLEs of the K decomposed witnesses of one side read from its packed digit
+ * planes (lf_fold_step_bufs.planes[side] of N elements, exactly as the step writes it;
+ * K = pr->K, tau = 3 at d = 24, else 1), without the u64 rows:
+ *   lf_dev_fhat_evaluate_planes(planes) = lf_dev_fhat_evaluate_eq(f_coeff_k, wstride N d, nw K)
+ *   lf_dev_fhat_lincomb_planes(planes)  = lf_dev_fhat_lincomb_digits(f_coeff_k, wstride N d, nw K)
+ * for f_coeff_k = lf_dev_expand_planes(planes): out [K][tau] NTT elements; eq: 2^nv NTT
+ * elements (lf_dev_eq_table); coef: K tau NTT elements; io: 2^nv NTT elements; all on the
+ * device. LF_ERR_UNSUPPORTED_RING where lf_fold_step_planes_len(pr, 1) is 0 (d = 2048,
+ * b_small != 2, K > 15); LF_ERR_INVALID_ARG for a NULL pointer or N > 2^nv. */
+int lf_dev_fhat_evaluate_planes(lf_ctx *ctx, const lf_params *pr, const uint64_t *planes, size_t N, int nv,
+                                const uint64_t *eq, uint64_t *out);
+int lf_dev_fhat_lincomb_planes(lf_ctx *ctx, const lf_params *pr, const uint64_t *planes, size_t N, int nv,
                                const uint64_t *coef, uint64_t *io);
 int lf_ctx_device(const lf_ctx *ctx);
 

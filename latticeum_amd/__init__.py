@@ -403,6 +403,30 @@ class Context:
         self.check(self.lib.lf_dev_fhat_lincomb_digits(self.h, d, _dptr(f_coeff), N, wstride, nw, nv, _dptr(coef),
                                                        _dptr(io)))
 
+    def dev_fhat_evaluate_planes(self, params: LfParams, planes, N: int, nv: int, eq, out):
+        """dev_fhat_evaluate_eq of one side's K decomposed witnesses read from its packed digit
+        planes (lf_fold_step_bufs.planes of N elements): out [K][tau][d]"""
+        self.check(self.lib.lf_dev_fhat_evaluate_planes(self.h, C.byref(params), _dptr(planes), N, nv, _dptr(eq),
+                                                        _dptr(out)))
+
+    def dev_fhat_lincomb_planes(self, params: LfParams, planes, N: int, nv: int, coef, io):
+        """dev_fhat_lincomb_digits of one side's K decomposed witnesses read from its packed planes"""
+        self.check(self.lib.lf_dev_fhat_lincomb_planes(self.h, C.byref(params), _dptr(planes), N, nv, _dptr(coef),
+                                                       _dptr(io)))
+
+    def sumcheck_prove_fold_planes(self, transcript: "Poseidon2Transcript", comb: "Comb", mles5, params: LfParams,
+                                   planes0, planes1, N: int, nv: int, work):
+        """sumcheck_prove_fold_digits with the 2K witnesses as the two sides' packed digit planes
+        (lf_sumcheck_prove_fold_planes)"""
+        d = params.d
+        tau = 3 if d == 24 else 1
+        proof = np.zeros(nv * 5 * d, np.uint64)
+        rnd = np.zeros(nv * tau, np.uint64)
+        self.check(self.lib.lf_sumcheck_prove_fold_planes(self.h, transcript.h, C.byref(comb.s), _dptr(mles5),
+                                                          C.byref(params), _dptr(planes0), _dptr(planes1), N, nv,
+                                                          _dptr(work), _ptr(proof), _ptr(rnd)))
+        return proof, rnd
+
     def dev_mle_fix_first(self, d: int, src, src_stride: int, nm: int, nv: int, r_base, out, out_stride: int):
         r = _u64(r_base)
         self.check(self.lib.lf_dev_mle_fix_first(self.h, d, _dptr(src), src_stride, nm, nv, _ptr(r), _dptr(out),
@@ -827,10 +851,12 @@ class CCSMatrices:
 
 class Prover:
     """fold() end to end (lf_fold_prove, zk_latticefold_prove): device scratch for one
-    (scheme, params, CCS) shape. The CCS gets its structure (l, degree, c, S) here."""
+    (scheme, params, CCS) shape. The CCS gets its structure (l, degree, c, S) here.
+    lean=True (lf_prover_create_lean): the decomposed witnesses are held as packed digit
+    planes only; the same outputs from less device memory."""
 
     def __init__(self, ctx: Context, scheme: "AjtaiCommitmentScheme", params: LfParams, ccs: CCSMatrices, l: int,
-                 degree: int, c, S, repr: int = REPR_CANONICAL):
+                 degree: int, c, S, repr: int = REPR_CANONICAL, lean: bool = False):
         self.ctx, self.lib, self.pr, self.ccs, self.scheme = ctx, ctx.lib, params, ccs, scheme
         c = _u64(c)
         off = np.zeros(len(S) + 1, np.int32)
@@ -839,7 +865,8 @@ class Prover:
         ctx.check(self.lib.lf_ccs_set_structure(ctx.h, ccs.h, l, degree, len(S), _ptr(c), _ptr(off), _ptr(idx), repr))
         h = C.c_void_p()
         self.lib.lf_ctx_set_error(ctx.h, b"")  # so a message read below is this call's
-        rc = self.lib.lf_prover_create(ctx.h, scheme.h, C.byref(params), ccs.h, C.byref(h))
+        create = self.lib.lf_prover_create_lean if lean else self.lib.lf_prover_create
+        rc = create(ctx.h, scheme.h, C.byref(params), ccs.h, C.byref(h))
         if rc:
             msg = self.lib.lf_ctx_last_error(ctx.h).decode()
             raise LfError(rc, msg or "lf_prover_create: " + self.lib.lf_status_string(rc).decode())
@@ -849,6 +876,16 @@ class Prover:
         self.tau = 3 if params.d == 24 else 1
         self.kappa = scheme.kappa
         self.c, self.S = c, [list(x) for x in S]
+
+    @property
+    def lean(self) -> bool:
+        """made with lean=True: the decomposed witnesses live as packed digit planes only"""
+        return bool(self.lib.lf_prover_is_lean(self.h))
+
+    @property
+    def device_bytes(self) -> int:
+        """bytes of the prover's carved device allocation"""
+        return int(self.lib.lf_prover_device_bytes(self.h))
 
     def replay(self, acc: dict, cm_i, x_ccs, proof: dict, repr: int = REPR_CANONICAL) -> dict:
         """the verifier-variable replay (fold_replay) of a proof this prover wrote"""

@@ -205,6 +205,9 @@ SIGNATURES = {
     "lf_ccs_is_scalar": (I, [VP]),
     "lf_ccs_is_reordered": (I, [VP]),
     "lf_prover_create": (I, [VP, VP, C.POINTER(LfParams), VP, C.POINTER(VP)]),
+    "lf_prover_create_lean": (I, [VP, VP, C.POINTER(LfParams), VP, C.POINTER(VP)]),
+    "lf_prover_is_lean": (I, [VP]),
+    "lf_prover_device_bytes": (SZ, [VP]),
     "lf_prover_destroy": (None, [VP]),
     "lf_prover_last_error": (C.c_char_p, [VP]),
     "lf_prover_timing": (I, [VP, I, VP]),
@@ -264,6 +267,10 @@ SIGNATURES = {
     "lf_dev_compute_x_s": (I, [VP, C.POINTER(LfParams), VP, SZ, VP]),
     "lf_fold_step_partial_len": (SZ, [VP, C.POINTER(LfParams)]),
     "lf_fold_step_planes_len": (SZ, [C.POINTER(LfParams), SZ]),
+    "lf_dev_fhat_evaluate_planes": (I, [VP, C.POINTER(LfParams), VP, SZ, I, VP, VP]),
+    "lf_dev_fhat_lincomb_planes": (I, [VP, C.POINTER(LfParams), VP, SZ, I, VP, VP]),
+    "lf_sumcheck_prove_fold_planes": (I, [VP, VP, C.POINTER(LfComb), VP, C.POINTER(LfParams), VP, VP, SZ, I, VP, VP,
+                                          VP]),
     "lf_dev_fold_step_partial": (I, [VP, VP, C.POINTER(LfParams), SZ, C.POINTER(LfFoldStepBufs), VP]),
     "lf_dev_fold_step_finish": (I, [VP, VP, C.POINTER(LfParams), SZ, C.POINTER(LfFoldStepBufs), VP]),
     "lf_dev_fold_step_sharded": (I, [VP, VP, C.POINTER(LfParams), SZ, C.POINTER(LfFoldStepBufs), VP]),

@@ -269,6 +269,8 @@ int get_tables(lf_ctx *c, int d, Tables *&out);  // negacyclic twiddle tables fo
 size_t partial_elems(const lf_ajtai *aj, int nvec);
 int ajtai_launch(lf_ctx *c, const lf_ajtai *aj, const uint64_t *const *vecs, int nvec, uint64_t *cm);
 int allreduce_modp(lf_ctx *c, lf_comm *cm, uint64_t *x, size_t n);
+// api_step.hip: can the step keep the decomposed witnesses as packed planes only? (lf_prover_create_lean)
+int step_packed_form(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr);
 
 // absorb R::from(value): the scalar in every NTT slot's base-ring word 0
 inline void absorb_scalar(lf_transcript *t, uint64_t value, int d) {

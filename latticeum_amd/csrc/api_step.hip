@@ -474,6 +474,29 @@ int step_commit(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, size_t W, co
 
 }  // namespace
 
+// LF_OK when a step of (scheme, params) with planes and neither f_k nor f_coeff_k runs a
+// fused decomposition (step_plan), so the planes can be the decomposed witnesses' only
+// form; else LF_ERR_INVALID_ARG with the reason in the context's last error
+int step_packed_form(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr) {
+  int lb, lbs;
+  LF_TRY(check_params(c, pr, lb, lbs));
+  if (pr->d != aj->d) return fail(c, LF_ERR_INVALID_ARG, "params ring != Ajtai ring");
+  if (lbs != 1) return fail(c, LF_ERR_INVALID_ARG, "no packed form: packed planes need b_small = 2");
+  if (pr->K > 15) return fail(c, LF_ERR_INVALID_ARG, "no packed form: packed planes hold K <= 15 digits");
+  if (!lf_fold_step_planes_len(pr, 1))
+    return fail(c, LF_ERR_INVALID_ARG, "no packed form at this ring degree (d = 24, 16 .. 512, 1024 or 4096)");
+  if (!aj->Af || aj->geom.Lp != pr->L)
+    return fail(c, LF_ERR_INVALID_ARG, "no packed form: the scheme has no fragments grouped by this L");
+  Tables *t;
+  LF_TRY(get_tables(c, pr->d, t));
+  uint64_t some;
+  lf_fold_step_bufs b{};
+  b.planes[0] = b.planes[1] = &some;  // never dereferenced: step_plan reads which buffers are given
+  if (step_plan(aj, pr, lbs, t, &b).dec == Decomp::Plain)
+    return fail(c, LF_ERR_INVALID_ARG, "no packed form: the step has no fused decomposition for this scheme and params");
+  return LF_OK;
+}
+
 extern "C" {
 
 int lf_dev_decompose_witness(lf_ctx *c, const lf_params *pr, const uint64_t *fc, size_t N, uint64_t *fck,

@@ -29,6 +29,14 @@ int comb_check(lf_ctx *c, const lf_comb *cb, int nm, int d, int degree, lfk::Com
   }
   return LF_OK;
 }
+// the *_planes entries: pr names a packed form (lf_fold_step_planes_len) of a supported ring
+int planes_check(lf_ctx *c, const lf_params *pr) {
+  if (!pr) return fail(c, LF_ERR_INVALID_ARG, "null params");
+  if (!lf_fold_step_planes_len(pr, 1))
+    return fail(c, LF_ERR_UNSUPPORTED_RING, "packed planes: d = 24, 16 .. 512, 1024 or 4096, b_small = 2, K <= 15");
+  int lb, lbs;
+  return check_params(c, pr, lb, lbs);
+}
 int comb_degree(const lf_comb *cb, int degree) { return cb->kind == LF_COMB_FOLDING ? 2 * cb->bsmall : degree; }
 
 // one round as its message producer sees it: the MLEs with i variables fixed
@@ -84,6 +92,7 @@ struct DigitFhat {
   const uint64_t *fc0, *fc1;
   int K;
   size_t N, wstride;
+  bool planes = false;  // fc0, fc1 are the sides' packed digit planes (lf_sumcheck_prove_fold_planes)
 };
 // Folding or (unsplit) linearization rounds: every message is one launch's round sums.
 // The fixed MLEs go to the context scratch and `alt` (the input itself when ptrs is null)
@@ -104,7 +113,10 @@ int sumcheck_run(lf_ctx *c, lf_transcript *t, const lf_comb *cb, const lfk::Comb
   uint64_t *buf = c->sc, *partial = buf + fixed, *ev = partial + part, *w = ev + (size_t)nev * d;
   if (wlen) LF_HIP(c, lfk::fold_weights(cb->mu, cb->nk, cb->tau, d, w, c->cur));
   auto message = [&](const Round &r, uint64_t *msg) {
-    if (dg && r.i == 0)  // round 0 straight from the digits (cur: the 5 general MLEs)
+    if (dg && r.i == 0 && dg->planes)  // round 0 straight from the planes
+      LF_HIP(c, lfk::round_folding0_planes(r.cur, r.stride, d, dg->K, dg->fc0, dg->fc1, dg->N, w, r.half, partial, ev,
+                                           c->cur));
+    else if (dg && r.i == 0)  // round 0 straight from the digits (cur: the 5 general MLEs)
       LF_HIP(c, lfk::round_folding0_digits(r.cur, r.stride, dg->fc0, dg->fc1, dg->K, dg->N, dg->wstride,
                                            cb->nk * cb->tau, w, r.half, d, partial, ev, c->cur));
     else if (cb->kind == LF_COMB_FOLDING)
@@ -114,7 +126,10 @@ int sumcheck_run(lf_ctx *c, lf_transcript *t, const lf_comb *cb, const lfk::Comb
     return download_msg(c, msg, ev, (size_t)nev * d);
   };
   auto fixed_digits = [&](const Round &r, const uint64_t *ch, uint64_t *dst) {
-    if (dg && r.i == 0 && dst)  // after the 5 general MLEs, the f_hat ones from the digits
+    if (dg && r.i == 0 && dst && dg->planes)
+      LF_HIP(c, lfk::fix_fhat_planes(d, dg->K, dg->fc0, dg->fc1, dg->N, r.half, ch, dst + 5 * r.half * d, r.half * d,
+                                     c->cur));
+    else if (dg && r.i == 0 && dst)  // after the 5 general MLEs, the f_hat ones from the digits
       LF_HIP(c, lfk::fix_fhat_digits(dg->fc0, dg->fc1, dg->K, dg->N, dg->wstride, nm - 5, r.half, d, ch,
                                      dst + 5 * r.half * d, r.half * d, c->cur));
     return (int)LF_OK;
@@ -329,6 +344,29 @@ int lf_dev_fhat_lincomb_digits(lf_ctx *c, int d, const uint64_t *f_coeff, size_t
   return LF_OK;
 }
 
+int lf_dev_fhat_evaluate_planes(lf_ctx *c, const lf_params *pr, const uint64_t *planes, size_t N, int nv,
+                                const uint64_t *eq, uint64_t *out) {
+  if (!c || !pr || !eq || !out || nv < 1 || nv > 40 || (N && !planes)) return LF_ERR_INVALID_ARG;
+  DevGuard g(c);
+  LF_TRY(planes_check(c, pr));
+  const size_t n = (size_t)1 << nv;
+  if (N > n) return fail(c, LF_ERR_INVALID_ARG, "N exceeds 2^nv");
+  const int d = pr->d, nm = pr->K * (d == 24 ? 3 : 1);
+  LF_TRY(grow(c, c->sc, c->sc_elems, lfk::mle_eval_partial_elems(d, nm)));
+  LF_HIP(c, lfk::fhat_dot_planes(d, pr->K, planes, N, eq, n, c->sc, out, c->cur));
+  return LF_OK;
+}
+
+int lf_dev_fhat_lincomb_planes(lf_ctx *c, const lf_params *pr, const uint64_t *planes, size_t N, int nv,
+                               const uint64_t *coef, uint64_t *io) {
+  if (!c || !pr || !coef || !io || nv < 0 || nv > 40 || (N && !planes)) return LF_ERR_INVALID_ARG;
+  DevGuard g(c);
+  LF_TRY(planes_check(c, pr));
+  if (N > ((size_t)1 << nv)) return fail(c, LF_ERR_INVALID_ARG, "N exceeds 2^nv");
+  LF_HIP(c, lfk::fhat_lincomb_planes(pr->d, pr->K, planes, N, coef, nv, io, c->cur));
+  return LF_OK;
+}
+
 static_assert(LF_PLAN_FOLDING == lfk::ROUND_FOLDING && LF_PLAN_LIN == lfk::ROUND_LIN &&
                   LF_PLAN_LIN_EQ == lfk::ROUND_LIN_EQ,
               "lf.h's plan kinds are the launchers' round kinds");
@@ -423,6 +461,23 @@ int lf_sumcheck_prove_fold_digits(lf_ctx *c, lf_transcript *t, const lf_comb *cb
   const int nm = 5 + cb->nk * cb->tau;
   LF_TRY(comb_check(c, cb, nm, d, 4, &cs));
   const DigitFhat dg{fc0, fc1, K, N, wstride};
+  return sumcheck_run(c, t, cb, cs, mles5, nullptr, work, nm, nv, d, 4, proof, randomness, &dg);
+}
+
+int lf_sumcheck_prove_fold_planes(lf_ctx *c, lf_transcript *t, const lf_comb *cb, const uint64_t *mles5,
+                                  const lf_params *pr, const uint64_t *planes0, const uint64_t *planes1, size_t N,
+                                  int nv, uint64_t *work, uint64_t *proof, uint64_t *randomness) {
+  if (!c || !t || !cb || !mles5 || !pr || !planes0 || !planes1 || !work || !proof || !randomness || nv < 1 || nv > 40)
+    return LF_ERR_INVALID_ARG;
+  DevGuard g(c);
+  LF_TRY(planes_check(c, pr));
+  const int d = pr->d, K = pr->K, tau = d == 24 ? 3 : 1;
+  if (cb->kind != LF_COMB_FOLDING || cb->bsmall != 2 || cb->nk != 2 * K || cb->tau != tau || N > ((size_t)1 << nv))
+    return fail(c, LF_ERR_INVALID_ARG, "fold_planes: a folding combination with B_SMALL = 2 over 2K witnesses, N <= 2^nv");
+  lfk::CombS cs;
+  const int nm = 5 + cb->nk * cb->tau;
+  LF_TRY(comb_check(c, cb, nm, d, 4, &cs));
+  const DigitFhat dg{planes0, planes1, K, N, 0, true};
   return sumcheck_run(c, t, cb, cs, mles5, nullptr, work, nm, nv, d, 4, proof, randomness, &dg);
 }
 

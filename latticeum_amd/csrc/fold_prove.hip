@@ -63,6 +63,11 @@ struct lf_prover {
   uint64_t *eq0 = nullptr, *mzw = nullptr;
   uint64_t *lev = nullptr;  // the live Mz MLEs at r_lin (the linearization sumcheck's final values)
   uint64_t *chk = nullptr;  // lf_lcccs_check / lf_cccs_check: the compare kernel's result words
+  // lean (lf_prover_create_lean): no fkc / fk; the decomposed witnesses are the packed
+  // digit planes of each side, and witness_checks takes its N elements from scr
+  bool lean = false;
+  uint64_t *planes[2] = {}, *scr = nullptr;
+  size_t mem_elems = 0;  // the carved allocation (lf_prover_device_bytes)
   std::string err;
   // every value the last lf_fold_prove sampled from its transcript, in order
   // (lf_fold_prove_vars replays the proof on them instead of a second sponge)
@@ -290,10 +295,13 @@ size_t carve(const std::vector<Part> &parts, size_t align, uint64_t *base) {
 int prover_alloc(lf_prover *P) {
   const size_t d = P->d, K = P->K, N = P->N, W = P->W, n = P->n, nn = P->nn, l = P->l, kd = P->kappa * d, tau = P->tau,
                t = P->t, s = P->s;
+  // the decomposed witnesses: their f_coeff_k / f_k rows, or (lean) packed planes and one N-element scratch
+  const size_t rows = P->lean ? 0 : K * N * d, pl = P->lean ? lf_fold_step_planes_len(&P->pr, N) : 0;
   const std::vector<Part> parts = {
       {&P->z, n * d}, {&P->mz, t * nn * d}, {&P->lin, (size_t)std::max(P->nlive, 1) * std::max<size_t>(nn / 4, 1) * d},
       {&P->pt, s * d}, {&P->beta, s * d}, {&P->val, (t + 3) * d},
-      {&P->fkc[0], K * N * d}, {&P->fkc[1], K * N * d}, {&P->fk[0], K * N * d}, {&P->fk[1], K * N * d},
+      {&P->fkc[0], rows}, {&P->fkc[1], rows}, {&P->fk[0], rows}, {&P->fk[1], rows},
+      {&P->planes[0], pl}, {&P->planes[1], pl}, {&P->scr, P->lean ? N * d : 0},
       {&P->wk[0], K * W * d}, {&P->wk[1], K * W * d}, {&P->y[0], K * kd}, {&P->y[1], K * kd},
       {&P->cmd[0], kd}, {&P->cmd[1], kd}, {&P->xw[0], (l + 1) * d}, {&P->xw[1], (l + 1) * d},
       {&P->xs, 2 * K * (l + 1) * d}, {&P->zdec[0], K * n * d}, {&P->zdec[1], K * n * d},
@@ -308,12 +316,19 @@ int prover_alloc(lf_prover *P) {
       {&P->hu[0], K * t * d}, {&P->hu[1], K * t * d}, {&P->hv[0], K * tau * d}, {&P->hv[1], K * tau * d},
       {&P->hr[0], s * d}, {&P->hr[1], s * d}, {&P->htheta, 2 * K * tau * d}, {&P->heta, 2 * K * t * d}};
   DevGuard g(P->device);
-  hipError_t e = hipMalloc(&P->mem, carve(parts, 32, nullptr) * 8);  // 256-B aligned parts
+  P->mem_elems = carve(parts, 32, nullptr);
+  hipError_t e = hipMalloc(&P->mem, P->mem_elems * 8);  // 256-B aligned parts
   if (e != hipSuccess) {
     P->mem = nullptr;
     return hip_status(e);
   }
   carve(parts, 32, P->mem);
+  // a zero-length part's address is the next part's: the decomposition must see NULL there
+  for (int side = 0; side < 2; side++) {
+    if (P->lean) P->fkc[side] = P->fk[side] = nullptr;
+    if (!P->lean) P->planes[side] = nullptr;
+  }
+  if (!P->lean) P->scr = nullptr;
   if (!P->act_host.empty()) {
     if (hipMemcpy(P->act, P->act_host.data(), P->act_host.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
       return LF_ERR_DEVICE;
@@ -588,7 +603,10 @@ void enqueue_decomposed_side(lf_prover *P, GroupFeed &E, const Fold &F, int side
   const int d = P->d, tau = P->tau, s = P->s, K = P->K, t = P->t, G = MZ_GROUP;
   const size_t N = P->N, n = P->n, l = P->l, kd = P->kappa * d;
   const uint64_t *eq_s = F.M + (size_t)(2 * side) * F.mstride;
-  Q.check(lf_dev_fhat_evaluate_eq(C, d, P->fkc[side], N, N * d, K, s, eq_s, P->vs + (size_t)side * K * tau * d), "v_s");
+  uint64_t *vs = P->vs + (size_t)side * K * tau * d;
+  Q.check(P->lean ? lf_dev_fhat_evaluate_planes(C, &P->pr, P->planes[side], N, s, eq_s, vs)
+                  : lf_dev_fhat_evaluate_eq(C, d, P->fkc[side], N, N * d, K, s, eq_s, vs),
+          "v_s");
   Q.d2p(P->hx[side], P->xs + (size_t)side * K * (l + 1) * d, (size_t)K * (l + 1) * d);
   Q.d2p(P->hy[side], P->y[side], (size_t)K * kd);
   Q.d2p(P->hv[side], P->vs + (size_t)side * K * tau * d, (size_t)K * tau * d);
@@ -622,8 +640,9 @@ int decomposition(lf_prover *P, Run &R, Fold &F) {
   b.acc_cm = P->cmd[0];
   b.cm = P->cmd[1];
   for (int side = 0; side < 2; side++) {
-    b.fk_coeff[side] = P->fkc[side];
+    b.fk_coeff[side] = P->fkc[side];  // lean: NULL, the planes are the decomposed witnesses' only form
     b.fk[side] = P->fk[side];
+    b.planes[side] = P->planes[side];
     b.wk[side] = P->wk[side];
     b.y[side] = P->y[side];
   }
@@ -721,7 +740,9 @@ int folding_mles(lf_prover *P, Run &R, Fold &F) {
           "challenged Mz");
   for (int side = 0; side < 2; side++) {
     uint64_t *g = M + (size_t)(2 * side + 1) * mstride;
-    if (F.digits)
+    if (P->lean)
+      R.check(lf_dev_fhat_lincomb_planes(C, &P->pr, P->planes[side], N, s, P->coef[side], g), "g");
+    else if (F.digits)
       R.hip(lfk::fhat_lincomb_digits(P->fkc[side], K, N, N * d, P->coef[side], s, d, g, R.st), "g");
     else
       R.check(lf_dev_mle_lincomb(C, d, M + (5 + (size_t)side * K * tau) * mstride, mstride, K * tau, s, P->coef[side], g),
@@ -741,7 +762,11 @@ int folding_sumcheck(lf_prover *P, Run &R, Fold &F) {
   cb.tau = P->tau;
   cb.bsmall = (int)P->pr.b_small;
   cb.mu = P->mu;
-  if (R.rc == LF_OK)
+  if (R.rc == LF_OK && P->lean)
+    R.check(lf_sumcheck_prove_fold_planes(P->ctx, R.T, &cb, F.M, &P->pr, P->planes[0], P->planes[1], N, s,
+                                          F.M + 5 * F.mstride, F.proof->fold_sumcheck, rnd.data()),
+            "folding sumcheck");
+  else if (R.rc == LF_OK)
     R.check(F.digits ? lf_sumcheck_prove_fold_digits(P->ctx, R.T, &cb, F.M, P->fkc[0], P->fkc[1], K, N, N * d, s, d,
                                                      F.M + 5 * F.mstride, F.proof->fold_sumcheck, rnd.data())
                      : lf_sumcheck_prove(P->ctx, R.T, &cb, F.M, P->nm_fold, s, d, 2 * cb.bsmall, F.proof->fold_sumcheck,
@@ -761,9 +786,12 @@ int evaluations(lf_prover *P, Run &R, Fold &F) {
   R.h2d(P->r0, F.r0.data(), (size_t)s * d);
   // one eq(r_0) table and one set of Mz weights at r_0 for both sides
   R.check(lf_dev_eq_table(C, d, P->r0, s, P->eq0), "eq(r_0)");
-  for (int side = 0; side < 2; side++)
-    R.check(lf_dev_fhat_evaluate_eq(C, d, P->fkc[side], N, N * d, K, s, P->eq0, P->theta + (size_t)side * K * tau * d),
+  for (int side = 0; side < 2; side++) {
+    uint64_t *th = P->theta + (size_t)side * K * tau * d;
+    R.check(P->lean ? lf_dev_fhat_evaluate_planes(C, &P->pr, P->planes[side], N, s, P->eq0, th)
+                    : lf_dev_fhat_evaluate_eq(C, d, P->fkc[side], N, N * d, K, s, P->eq0, th),
             "theta");
+  }
   R.d2p(P->htheta, P->theta, 2 * (size_t)K * tau * d);
   R.hip(hipEventRecord(P->ev[0], R.st), "event");
   R.check(lf_dev_mz_weights(C, P->ccs, s, P->eq0, P->mzw), "eta weights");
@@ -865,7 +893,8 @@ int witness_checks(lf_prover *P, Run &R, const lf_witness *w, const uint64_t *cm
   const int d = P->d;
   const size_t N = P->N, W = P->W, kd = P->kappa * d;
   *failed = LF_REL_OK;
-  uint64_t *fc = P->fkc[0], *wc = P->wk[0];  // N and W elements of the decomposition's planes
+  // N and W elements of the decomposition's buffers (lean: its N-element scratch)
+  uint64_t *fc = P->lean ? P->scr : P->fkc[0], *wc = P->wk[0];
   R.check(lf_dev_witness_from_f(C, &P->pr, w->f, N, fc, wc), "Witness::from_f");
   if (R.rc) return R.rc;
   R.hip(lfk::first_diff(fc, w->f_coeff, N * d, P->chk, R.st), "compare f_coeff");
@@ -899,7 +928,8 @@ void assemble_z(lf_prover *P, Run &R, const uint64_t *x, const uint64_t *h, cons
 
 extern "C" {
 
-int lf_prover_create(lf_ctx *ctx, const lf_ajtai *aj, const lf_params *pr, const lf_ccs *ccs, lf_prover **out) {
+static int prover_create(lf_ctx *ctx, const lf_ajtai *aj, const lf_params *pr, const lf_ccs *ccs, bool lean,
+                         lf_prover **out) {
   if (!ctx || !aj || !pr || !ccs || !out) return LF_ERR_INVALID_ARG;
   *out = nullptr;
   auto P = std::make_unique<lf_prover>();
@@ -908,7 +938,12 @@ int lf_prover_create(lf_ctx *ctx, const lf_ajtai *aj, const lf_params *pr, const
   P->ccs = ccs;
   P->pr = *pr;
   P->device = lf_ctx_device(ctx);
+  P->lean = lean;
   LF_TRY(prover_shape(P.get()));
+  if (lean) {
+    DevGuard g(P->device);
+    LF_TRY(step_packed_form(ctx, aj, pr));
+  }
   linearization_mle_list(P.get());
   LF_TRY(live_matrix_order(P.get()));
   active_points(P.get());
@@ -916,6 +951,18 @@ int lf_prover_create(lf_ctx *ctx, const lf_ajtai *aj, const lf_params *pr, const
   *out = P.release();
   return LF_OK;
 }
+
+int lf_prover_create(lf_ctx *ctx, const lf_ajtai *aj, const lf_params *pr, const lf_ccs *ccs, lf_prover **out) {
+  return prover_create(ctx, aj, pr, ccs, false, out);
+}
+
+int lf_prover_create_lean(lf_ctx *ctx, const lf_ajtai *aj, const lf_params *pr, const lf_ccs *ccs, lf_prover **out) {
+  return prover_create(ctx, aj, pr, ccs, true, out);
+}
+
+int lf_prover_is_lean(const lf_prover *P) { return P && P->lean ? 1 : 0; }
+
+size_t lf_prover_device_bytes(const lf_prover *P) { return P ? P->mem_elems * 8 : 0; }
 
 void lf_prover_destroy(lf_prover *P) { delete P; }
 

@@ -357,6 +357,20 @@ hipError_t fix_fhat_digits(const uint64_t *fc0, const uint64_t *fc1, int K, size
 // io[x] += sum_(k, j) coef[k tau + j] fhat_(k, j)[x] for the nw digit witnesses of fc (2^nv points)
 hipError_t fhat_lincomb_digits(const uint64_t *fc, int nw, size_t N, size_t wstride, const uint64_t *coef, int nv,
                                int d, uint64_t *io, hipStream_t st);
+// The four f_hat readers above over one side's packed digit planes (lf_fold_step_bufs.planes
+// of K planes, N elements, b_small = 2; digitpack.hpp's public formats: d = 24, 16 .. 512,
+// 1024, 4096, K <= 15) instead of coefficient rows; the same field elements.
+// out [K][tau] = sum_x eq[x] (.) fhat_(k, j)[x] (fhat_dot; partial: mle_eval_partial_elems(d, K tau))
+hipError_t fhat_dot_planes(int d, int K, const uint64_t *planes, size_t N, const uint64_t *eq, size_t n,
+                           uint64_t *partial, uint64_t *out, hipStream_t st);
+hipError_t fhat_lincomb_planes(int d, int K, const uint64_t *planes, size_t N, const uint64_t *coef, int nv,
+                               uint64_t *io, hipStream_t st);
+// round_folding0_digits / fix_fhat_digits with side 0's planes and side 1's (nf = 2 K tau)
+hipError_t round_folding0_planes(const uint64_t *mles, size_t stride, int d, int K, const uint64_t *planes0,
+                                 const uint64_t *planes1, size_t N, const uint64_t *w, size_t half,
+                                 uint64_t *partial, uint64_t *evals, hipStream_t st);
+hipError_t fix_fhat_planes(int d, int K, const uint64_t *planes0, const uint64_t *planes1, size_t N, size_t half,
+                           const uint64_t *r_base, uint64_t *out, size_t out_stride, hipStream_t st);
 hipError_t round_lin(const uint64_t *mles, size_t stride, int nm, const uint64_t *c, const CombS &cs, int degree,
                      size_t half, int d, uint64_t *partial, uint64_t *evals, hipStream_t st,
                      const uint64_t *const *ptrs = nullptr);

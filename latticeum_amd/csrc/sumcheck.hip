@@ -1224,4 +1224,408 @@ hipError_t assemble_z(const uint64_t *x, const uint64_t *w, int nz, size_t l1, s
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------- f_hat from the packed digit planes
+// The four f_hat consumers of the folding prover (k_fhat_dot, k_fhat_lincomb_digits,
+// k_round_folding0_digits, k_fix_fhat_digits) over lf_fold_step_bufs.planes instead of
+// the [K][N][d] u64 coefficient rows: the same field elements, the digit of (plane k,
+// element x, coefficient c) decoded by digitpack.hpp's functions. A digit source is one
+// side's buffer: word(x, c, k) loads what holds the digit, digit(word, c, k) decodes
+// it. PER_PLANE = false (the 16-bit sign|magnitude formats): one word holds the
+// coefficient's digits of all K planes, so a thread loads it once.
+namespace {
+
+struct PlMask24 {  // d = 24: [K][N] digit masks
+  static constexpr bool PER_PLANE = true;
+  using Word = uint2;
+  const uint2 *p;
+  size_t N;
+  int K;
+  __device__ __forceinline__ Word word(size_t x, int, int k) const { return p[mask24_index(k, N, x)]; }
+  __device__ __forceinline__ static int digit(Word w, int c, int) { return mask24_digit(w.x, w.y, c); }
+};
+struct PlSm1024 {  // d = 1024: sm16 words
+  static constexpr bool PER_PLANE = false;
+  using Word = uint32_t;
+  const uint32_t *p;
+  size_t N;
+  int K;
+  __device__ __forceinline__ Word word(size_t x, int c, int) const {
+    return p[sm1024_word_of(x, c)] >> (16 * sm1024_half_of(c));
+  }
+  __device__ __forceinline__ static int digit(Word w, int, int k) { return sm16_digit(w, k); }
+};
+struct PlSmp2 {  // d = 16 .. 512: sm16 words
+  static constexpr bool PER_PLANE = false;
+  using Word = uint32_t;
+  const uint32_t *p;
+  size_t N;
+  int K, d;
+  __device__ __forceinline__ Word word(size_t x, int c, int) const {
+    return p[smp2_word_of(x, d, c)] >> (16 * smp2_half_of(d, c));
+  }
+  __device__ __forceinline__ static int digit(Word w, int, int k) { return sm16_digit(w, k); }
+};
+struct PlSm8 {  // d = 4096: digit bytes
+  static constexpr bool PER_PLANE = true;
+  using Word = uint32_t;
+  const uint8_t *p;
+  size_t N;
+  int K;
+  __device__ __forceinline__ Word word(size_t x, int c, int k) const { return p[sm8_byte_of(x, K, k, c & 1023)]; }
+  __device__ __forceinline__ static int digit(Word w, int c, int) { return sm8_digit(w, c >> 10); }
+};
+
+// block_partial for the first nvalid (the same in every thread of the block) of NE values
+template <int TB, int NE>
+__device__ __forceinline__ void block_partial_upto(const Sv<TB> (&acc)[NE], int nvalid, int spb, int ppb, int slot,
+                                                   int lane_p, int d, uint64_t *dst) {
+  __shared__ uint64_t red[RT * TB];
+#pragma unroll
+  for (int e = 0; e < NE; e++)
+    if (e < nvalid) {  // uniform: every thread of the block meets the same barriers
+      s_store(red + threadIdx.x * TB, acc[e]);
+      __syncthreads();
+      for (int w = ppb / 2; w > 0; w >>= 1) {
+        if (lane_p < w) {
+          const int o = threadIdx.x + w * spb;
+          s_store(red + threadIdx.x * TB, s_add(s_load<TB>(red + threadIdx.x * TB), s_load<TB>(red + o * TB)));
+        }
+        __syncthreads();
+      }
+      if (lane_p == 0) s_store(dst + (size_t)e * d + slot * TB, s_load<TB>(red + threadIdx.x * TB));
+      __syncthreads();
+    }
+}
+
+// k_fhat_dot's sums: out[k][j] = sum_x eq[x] (.) digit(k, x, j ns + slot). A digit is a
+// sign, so a term is eq[x], p - eq[x] or nothing: every (plane, j, word) keeps a 64-bit
+// sum and its count of carries, reduced once at the end (sum + 2^64 carries), and no
+// product is formed. A thread covers the planes k0 .. k0 + KC (blockIdx.z = k0 / KC) and
+// all tau MLEs of each, and reads eq[x] once for all of them.
+template <int TB, class S, int KC>
+__global__ void __launch_bounds__(RT) k_fhat_dot_planes(S src, int K, size_t N, const uint64_t *eq, size_t n, int d,
+                                                        int spb, int nsplit, uint64_t *partial, int nm) {
+  constexpr int tau = TB == 3 ? 3 : 1;
+  const int slot_l = threadIdx.x % spb, lane_p = threadIdx.x / spb, ppb = RT / spb;
+  const int slot = blockIdx.y * spb + slot_l, ns = d / TB;
+  const int k0 = blockIdx.z * KC;
+  uint64_t lo[KC][tau][TB];
+  uint32_t cy[KC][tau][TB];
+#pragma unroll
+  for (int kk = 0; kk < KC; kk++)
+#pragma unroll
+    for (int j = 0; j < tau; j++)
+#pragma unroll
+      for (int q = 0; q < TB; q++) lo[kk][j][q] = 0, cy[kk][j][q] = 0;
+  for (size_t x = (size_t)blockIdx.x * ppb + lane_p; x < n && x < N; x += (size_t)nsplit * ppb) {
+    const Sv<TB> e = s_load<TB>(eq + x * d + slot * TB);
+    uint64_t ne[TB];  // -eq[x] (p for 0: the same residue)
+#pragma unroll
+    for (int q = 0; q < TB; q++) ne[q] = gl::P - e.c[q];
+#pragma unroll
+    for (int j = 0; j < tau; j++) {
+      const int c = j * ns + slot;
+      typename S::Word w{};
+      if (!S::PER_PLANE) w = src.word(x, c, 0);
+#pragma unroll
+      for (int kk = 0; kk < KC; kk++) {
+        const int k = k0 + kk;
+        if (k < K) {
+          if (S::PER_PLANE) w = src.word(x, c, k);
+          const int dg = S::digit(w, c, k);
+#pragma unroll
+          for (int q = 0; q < TB; q++) {
+            const uint64_t v = dg > 0 ? e.c[q] : dg < 0 ? ne[q] : 0;
+            uint64_t t;
+            cy[kk][j][q] += gl::addc64(lo[kk][j][q], v, t);
+            lo[kk][j][q] = t;
+          }
+        }
+      }
+    }
+  }
+  Sv<TB> acc[KC * tau];
+#pragma unroll
+  for (int kk = 0; kk < KC; kk++)
+#pragma unroll
+    for (int j = 0; j < tau; j++)
+#pragma unroll
+      for (int q = 0; q < TB; q++) {
+        gl::CAcc a;
+        gl::cacc_zero(a);
+        a.s0 = lo[kk][j][q];
+        a.c0 = cy[kk][j][q];
+        acc[kk * tau + j].c[q] = gl::cacc_reduce(a);
+      }
+  const int nk = K - k0 < KC ? K - k0 : KC;
+  block_partial_upto<TB, KC * tau>(acc, nk * tau, spb, ppb, slot, lane_p, d,
+                                   partial + ((size_t)blockIdx.x * nm + (size_t)k0 * tau) * d);
+}
+
+// k_fhat_lincomb_digits over one side's planes
+template <int TB, class S>
+__global__ void k_fhat_lincomb_planes(S src, int K, size_t N, const uint64_t *coef, size_t npts, int d, uint64_t *io) {
+  constexpr int tau = TB == 3 ? 3 : 1;
+  const int ns = d / TB;
+  const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  if (i >= npts * ns) return;
+  const size_t x = i / ns;
+  const int s = (int)(i - x * ns);
+  Sv<TB> pos = s_zero<TB>(), neg = s_zero<TB>();
+  if (x < N)
+    for (int j = 0; j < tau; j++) {
+      const int c = j * ns + s;
+      typename S::Word w{};
+      if (!S::PER_PLANE) w = src.word(x, c, 0);
+      for (int k = 0; k < K; k++) {
+        if (S::PER_PLANE) w = src.word(x, c, k);
+        const int a = S::digit(w, c, k);
+        if (a) {
+          const Sv<TB> cf = s_load<TB>(coef + (size_t)(k * tau + j) * d + s * TB);
+          if (a > 0)
+            pos = s_add(pos, cf);
+          else
+            neg = s_add(neg, cf);
+        }
+      }
+    }
+  uint64_t *o = io + x * d + s * TB;
+  s_store(o, s_add(s_load<TB>(o), s_sub(pos, neg)));
+}
+
+// k_round_folding0_digits with the digit pair (a, bv) of points 2b and 2b + 1 from the
+// planes (s0: side 0's K planes, s1: side 1's); f = (kg, j), kg < 2K, as there
+template <int TB, class S>
+__global__ void __launch_bounds__(RT) k_round_folding0_planes(const uint64_t *mles, size_t stride, S s0, S s1, int K,
+                                                              size_t N, int nf, const uint64_t *w, size_t half, int d,
+                                                              int spb, uint64_t *partial) {
+  constexpr int tau = TB == 3 ? 3 : 1;
+  static_assert(S::PER_PLANE || tau == 1, "one word per (point, slot) needs tau = 1");
+  const int slot_l = threadIdx.x % spb, lane_p = threadIdx.x / spb, ppb = RT / spb;
+  const int slot = blockIdx.y * spb + slot_l, ns = d / TB;
+  const int chunk = blockIdx.z, nchunk = gridDim.z;
+  const int f0 = (int)((long)nf * chunk / nchunk), f1 = (int)((long)nf * (chunk + 1) / nchunk);
+  constexpr int degree = 4;
+  Sv<TB> acc[degree + 1];
+#pragma unroll
+  for (int e = 0; e <= degree; e++) acc[e] = s_zero<TB>();
+  Sv<TB> w12 = s_zero<TB>();
+  for (int f = f0; f < f1; f++) w12 = s_add(w12, s_load<TB>(w + (size_t)f * d + slot * TB));
+  w12 = s_smul(w12, 12);
+  for (size_t b = (size_t)blockIdx.x * ppb + lane_p; b < half; b += (size_t)gridDim.x * ppb) {
+    const size_t x0 = 2 * b;
+    // the sign|magnitude formats: a side's K digits of a point from one word (a zero word past N)
+    typename S::Word wd[2][2] = {};
+    if (!S::PER_PLANE) {
+      if (x0 < N) wd[0][0] = s0.word(x0, slot, 0), wd[1][0] = s1.word(x0, slot, 0);
+      if (x0 + 1 < N) wd[0][1] = s0.word(x0 + 1, slot, 0), wd[1][1] = s1.word(x0 + 1, slot, 0);
+    }
+    SmallAcc A[3][TB];
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+#pragma unroll
+      for (int q = 0; q < TB; q++) A[k][q] = SmallAcc{0, 0, 0};
+    for (int f = f0; f < f1; f++) {
+      const int kg = f / tau, j = f - kg * tau, c = j * ns + slot;
+      const bool side = kg >= K;
+      const int k = side ? kg - K : kg;
+      int a, bv;
+      if (S::PER_PLANE) {
+        const S &sr = side ? s1 : s0;
+        a = x0 < N ? S::digit(sr.word(x0, c, k), c, k) : 0;
+        bv = x0 + 1 < N ? S::digit(sr.word(x0 + 1, c, k), c, k) : 0;
+      } else {
+        a = S::digit(side ? wd[1][0] : wd[0][0], c, k);
+        bv = S::digit(side ? wd[1][1] : wd[0][1], c, k);
+      }
+      const int dd = bv - a;
+      const uint32_t c1 = (uint32_t)((3 * a * a - 1) * dd + 12), c2 = (uint32_t)(3 * a * dd * dd + 12),
+                     c3 = (uint32_t)(dd * dd * dd + 12);
+      const Sv<TB> wf = s_load<TB>(w + (size_t)f * d + slot * TB);
+#pragma unroll
+      for (int q = 0; q < TB; q++) {
+        small_mad(A[0][q], wf.c[q], c1);
+        small_mad(A[1][q], wf.c[q], c2);
+        small_mad(A[2][q], wf.c[q], c3);
+      }
+    }
+    Sv<TB> Ak[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+#pragma unroll
+      for (int q = 0; q < TB; q++) Ak[k].c[q] = small_final(A[k][q]);
+      Ak[k] = s_sub(Ak[k], w12);
+    }
+    const uint64_t *pb = mles + 2 * b * d + slot * TB;
+    Sv<TB> v[5], sv[5];
+#pragma unroll
+    for (int m = 0; m < 5; m++) {
+      const uint64_t *p = pb + (size_t)m * stride;
+      v[m] = s_load<TB>(p);
+      sv[m] = s_sub(s_load<TB>(p + d), v[m]);
+    }
+#pragma unroll
+    for (int e = 0; e <= degree; e++) {
+      const Sv<TB> S_e = s_smul(s_add(s_smul(s_add(s_smul(Ak[2], e), Ak[1]), e), Ak[0]), e);
+      Sv<TB> t = s_mul(v[4], S_e);
+      if (chunk == 0) t = s_add(t, s_add(s_mul(v[0], v[1]), s_mul(v[2], v[3])));
+      acc[e] = s_add(acc[e], t);
+#pragma unroll
+      for (int m = 0; m < 5; m++) v[m] = s_add(v[m], sv[m]);
+    }
+  }
+  block_partial<TB, degree + 1>(acc, spb, ppb, slot, lane_p, d,
+                                partial + ((size_t)chunk * gridDim.x + blockIdx.x) * (degree + 1) * d);
+}
+
+// a + r (bv - a) for digits a, bv (k_fix_fhat_digits' value)
+template <int TB>
+__device__ __forceinline__ Sv<TB> fix_digit_pair(int a, int bv, const Sv<TB> &r) {
+  const int dd = bv - a;
+  Sv<TB> o;
+#pragma unroll
+  for (int q = 0; q < TB; q++) {
+    const uint64_t m = gl::mul(r.c[q], (uint64_t)(dd < 0 ? -dd : dd));
+    o.c[q] = dd < 0 ? gl::neg(m) : m;
+  }
+  o.c[0] = gl::add(o.c[0], a < 0 ? gl::P - 1 : (uint64_t)a);
+  return o;
+}
+
+// k_fix_fhat_digits from the planes. PER_PLANE: a thread per (f, b, slot) as there; the
+// sign|magnitude formats: a thread per (side, b, slot) writes its K planes' values from
+// the two words it loads (tau = 1, f = side K + k)
+template <int TB, class S>
+__global__ void k_fix_fhat_planes(S s0, S s1, int K, size_t N, int nf, size_t half, int d, Sv<TB> r, uint64_t *out,
+                                  size_t out_stride) {
+  constexpr int tau = TB == 3 ? 3 : 1;
+  static_assert(S::PER_PLANE || tau == 1, "one word per (point, slot) needs tau = 1");
+  const int ns = d / TB;
+  const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;  // (f or side, b, slot)
+  const int ng = S::PER_PLANE ? nf : 2;
+  if (i >= (size_t)ng * half * ns) return;
+  const size_t gb = i / ns;
+  const int s = (int)(i - gb * ns);
+  const int g = (int)(gb / half);
+  const size_t b = gb - (size_t)g * half, x0 = 2 * b;
+  if (S::PER_PLANE) {
+    const int kg = g / tau, j = g - kg * tau, c = j * ns + s;
+    const bool side = kg >= K;
+    const int k = side ? kg - K : kg;
+    const S &sr = side ? s1 : s0;
+    const int a = x0 < N ? S::digit(sr.word(x0, c, k), c, k) : 0;
+    const int bv = x0 + 1 < N ? S::digit(sr.word(x0 + 1, c, k), c, k) : 0;
+    s_store(out + (size_t)g * out_stride + b * d + s * TB, fix_digit_pair<TB>(a, bv, r));
+  } else {
+    const S &sr = g ? s1 : s0;
+    typename S::Word wa{}, wb{};
+    if (x0 < N) wa = sr.word(x0, s, 0);
+    if (x0 + 1 < N) wb = sr.word(x0 + 1, s, 0);
+    for (int k = 0; k < K; k++)
+      s_store(out + (size_t)(g * K + k) * out_stride + b * d + s * TB,
+              fix_digit_pair<TB>(S::digit(wa, s, k), S::digit(wb, s, k), r));
+  }
+}
+
+template <int V>
+struct IntC {
+  static constexpr int value = V;
+};
+// fn(IntC<TB>, side 0's source, side 1's source) for the format of degree d
+template <class Fn>
+hipError_t with_planes(int d, int K, size_t N, const uint64_t *p0, const uint64_t *p1, Fn fn) {
+  if (K < 1 || K > 15) return hipErrorInvalidValue;
+  if (d == 24)
+    return fn(IntC<3>{}, PlMask24{reinterpret_cast<const uint2 *>(p0), N, K},
+              PlMask24{reinterpret_cast<const uint2 *>(p1), N, K});
+  if (d == 1024)
+    return fn(IntC<1>{}, PlSm1024{reinterpret_cast<const uint32_t *>(p0), N, K},
+              PlSm1024{reinterpret_cast<const uint32_t *>(p1), N, K});
+  if (d == 4096)
+    return fn(IntC<1>{}, PlSm8{reinterpret_cast<const uint8_t *>(p0), N, K},
+              PlSm8{reinterpret_cast<const uint8_t *>(p1), N, K});
+  if (smp2_degree(d))
+    return fn(IntC<1>{}, PlSmp2{reinterpret_cast<const uint32_t *>(p0), N, K, d},
+              PlSmp2{reinterpret_cast<const uint32_t *>(p1), N, K, d});
+  return hipErrorInvalidValue;
+}
+
+}  // namespace
+
+// planes a thread of k_fhat_dot_planes covers (grid.z = ceil(K / it)). Phi_72: one plane,
+// its tau MLEs x 3 words = 9 sums; the dot plan gives at most 64 blocks along the points,
+// so the planes are what fills the chip (3 planes a thread measured 0.20 ms against 0.11 ms
+// at N = 98 815, eq staying in cache). X^d + 1: every plane (K <= 15 sums) from one word.
+static constexpr int DOT_KC3 = 1, DOT_KC1 = 15;
+
+hipError_t fhat_dot_planes(int d, int K, const uint64_t *planes, size_t N, const uint64_t *eq, size_t n,
+                           uint64_t *partial, uint64_t *out, hipStream_t st) {
+  if (!n) return hipSuccess;
+  const int tb = slot_words(d), ns = d / tb, nm = K * (tb == 3 ? 3 : 1);
+  const DotPlan pl = dot_plan(d, n);
+  const int spb = pl.spb, nsplit = pl.nsplit;
+  hipError_t e = with_planes(d, K, N, planes, planes, [&](auto tbc, auto src, auto) {
+    constexpr int TB = decltype(tbc)::value, KC = TB == 3 ? DOT_KC3 : DOT_KC1;
+    using S = decltype(src);
+    const dim3 grid((unsigned)nsplit, (unsigned)(ns / spb), (unsigned)((K + KC - 1) / KC));
+    hipLaunchKernelGGL((k_fhat_dot_planes<TB, S, KC>), grid, dim3(RT), 0, st, src, K, N, eq, n, d, spb, nsplit,
+                       partial, nm);
+    return hipGetLastError();
+  });
+  if (e != hipSuccess) return e;
+  const size_t len = (size_t)nm * d;
+  hipLaunchKernelGGL(k_sum_partials, dim3((unsigned)len), dim3(256), 0, st, partial, nsplit, len, out);
+  return hipGetLastError();
+}
+
+hipError_t fhat_lincomb_planes(int d, int K, const uint64_t *planes, size_t N, const uint64_t *coef, int nv,
+                               uint64_t *io, hipStream_t st) {
+  const size_t npts = (size_t)1 << nv, n = npts * (size_t)(d / slot_words(d));
+  return with_planes(d, K, N, planes, planes, [&](auto tbc, auto src, auto) {
+    constexpr int TB = decltype(tbc)::value;
+    using S = decltype(src);
+    hipLaunchKernelGGL((k_fhat_lincomb_planes<TB, S>), dim3(blocks(n, 256)), dim3(256), 0, st, src, K, N, coef, npts,
+                       d, io);
+    return hipGetLastError();
+  });
+}
+
+hipError_t round_folding0_planes(const uint64_t *mles, size_t stride, int d, int K, const uint64_t *planes0,
+                                 const uint64_t *planes1, size_t N, const uint64_t *w, size_t half,
+                                 uint64_t *partial, uint64_t *evals, hipStream_t st) {
+  if (!half) return hipErrorInvalidValue;
+  const int nf = 2 * K * (slot_words(d) == 3 ? 3 : 1);
+  const RoundPlan pl = round_plan(d, half, nf, ROUND_FOLDING);
+  const int spb = pl.spb;
+  const dim3 grid = plan_grid(pl);
+  hipError_t e = with_planes(d, K, N, planes0, planes1, [&](auto tbc, auto s0, auto s1) {
+    constexpr int TB = decltype(tbc)::value;
+    using S = decltype(s0);
+    hipLaunchKernelGGL((k_round_folding0_planes<TB, S>), grid, dim3(RT), 0, st, mles, stride, s0, s1, K, N, nf, w,
+                       half, d, spb, partial);
+    return hipGetLastError();
+  });
+  if (e != hipSuccess) return e;
+  const size_t len = (size_t)5 * d;
+  hipLaunchKernelGGL(k_sum_partials, dim3((unsigned)len), dim3(256), 0, st, partial, (int)(grid.x * grid.z), len,
+                     evals);
+  return hipGetLastError();
+}
+
+hipError_t fix_fhat_planes(int d, int K, const uint64_t *planes0, const uint64_t *planes1, size_t N, size_t half,
+                           const uint64_t *r_base, uint64_t *out, size_t out_stride, hipStream_t st) {
+  if (!half) return hipSuccess;
+  const int tb = slot_words(d), nf = 2 * K * (tb == 3 ? 3 : 1);
+  return with_planes(d, K, N, planes0, planes1, [&](auto tbc, auto s0, auto s1) {
+    constexpr int TB = decltype(tbc)::value;
+    using S = decltype(s0);
+    const size_t n = (size_t)(S::PER_PLANE ? nf : 2) * half * (d / TB);
+    Sv<TB> r;
+    for (int i = 0; i < TB; i++) r.c[i] = r_base[i];
+    hipLaunchKernelGGL((k_fix_fhat_planes<TB, S>), dim3(blocks(n, 256)), dim3(256), 0, st, s0, s1, K, N, nf, half, d,
+                       r, out, out_stride);
+    return hipGetLastError();
+  });
+}
+
 }  // namespace lfk

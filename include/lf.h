@@ -264,6 +264,13 @@ int lf_witness_from_w_ccs(lf_ctx *ctx, const lf_params *pr, const uint64_t *w_cc
                           uint64_t *f_coeff, uint64_t *f, int repr);
 int lf_witness_from_f(lf_ctx *ctx, const lf_params *pr, const uint64_t *f, size_t N,
                       uint64_t *f_coeff, uint64_t *w_ccs, int repr);
+/* Witness::from_f_coeff (arith.rs:324-338): f = CRT(f_coeff) over N elements, w_ccs =
+ * gadget_recompose(f, B, L) over N / L. f_coeff is any canonical residues (nothing about
+ * smallness is assumed) and is left unchanged. LF_ERR_INCORRECT_LENGTH when N is not a
+ * multiple of L, LF_ERR_UNSUPPORTED_RING for an unsupported d, LF_ERR_INVALID_ARG for a
+ * NULL pointer. */
+int lf_witness_from_f_coeff(lf_ctx *ctx, const lf_params *pr, const uint64_t *f_coeff, size_t N,
+                            uint64_t *f, uint64_t *w_ccs, int repr);
 /* f_coeff (N) -> f_coeff_k [K][N], f_k [K][N], w_ccs_k [K][N/L] */
 int lf_decompose_witness(lf_ctx *ctx, const lf_params *pr, const uint64_t *f_coeff, size_t N,
                          uint64_t *f_coeff_k, uint64_t *f_k, uint64_t *w_ccs_k, int repr);
@@ -314,6 +321,9 @@ int lf_dev_witness_from_w_ccs(lf_ctx *ctx, const lf_params *pr, const uint64_t *
                               uint64_t *f_coeff, uint64_t *f);
 int lf_dev_witness_from_f(lf_ctx *ctx, const lf_params *pr, const uint64_t *f, size_t N,
                           uint64_t *f_coeff, uint64_t *w_ccs);
+/* as lf_witness_from_f_coeff on device buffers (16-byte aligned), asynchronous */
+int lf_dev_witness_from_f_coeff(lf_ctx *ctx, const lf_params *pr, const uint64_t *f_coeff, size_t N,
+                                uint64_t *f, uint64_t *w_ccs);
 int lf_dev_decompose_witness(lf_ctx *ctx, const lf_params *pr, const uint64_t *f_coeff, size_t N,
                              uint64_t *f_coeff_k, uint64_t *f_k, uint64_t *w_ccs_k);
 /* nvec (<= 32) vectors of width() NTT elements each -> cm [nvec][kappa] */
@@ -829,6 +839,46 @@ int lf_lcccs_deserialize(const uint8_t *in, size_t len, int d, int repr, uint64_
                          lf_lcccs *out);
 int lf_lfproof_serialize(const lf_lfproof *proof, int repr, uint8_t *out, size_t cap, size_t *len);
 
+/* ------------------------------------------------------------ witness wire format
+ * The third object of an IVC state, beside the LCCCS and the LFProof. Only f_coeff is
+ * stored: f and w_ccs are functions of it (Witness::from_f_coeff) and are rebuilt on the
+ * device when the bytes are read. A coefficient is stored as its centred representative
+ * (x if x <= (p - 1) / 2, else x - p) at one of three widths:
+ *   bits = 16, 32: two's-complement, little-endian;  bits = 64: the canonical residue itself.
+ * Payload: N d integers in f_coeff's own order (coefficient c of element e at index
+ * e d + c), no padding. On the device the payload pointer is 16-byte aligned.
+ * Wire bytes: a 32-byte little-endian header, then the payload (32 + N d bits / 8 bytes):
+ *   0-3 ASCII "LFW1" | 4-7 u32 d | 8-11 u32 L | 12-15 u32 bits | 16-23 u64 N | 24-31 u64 0
+ *
+ *   lf_witness_packed_len: payload bytes; 0 for an unsupported d or width, or when the
+ *     size does not fit size_t.
+ *   lf_dev_witness_bits (synchronous): *norm = the l_inf norm on signed representatives;
+ *     *bits = the narrowest width that holds every coefficient: 16 iff all lie in
+ *     [-2^15, 2^15 - 1], else 32 iff all lie in [-2^31, 2^31 - 1], else 64.
+ *   lf_dev_witness_pack (asynchronous, one launch): a coefficient that does not fit
+ *     `bits` raises the context's overflow flag (lf_ctx_sync: LF_ERR_DECOMPOSITION_OVERFLOW).
+ *   lf_dev_witness_unpack (asynchronous): f_coeff in canonical form and, unless f and
+ *     w_ccs are both NULL, f and w_ccs as lf_dev_witness_from_f_coeff gives them, from one
+ *     read of the packed words. At bits = 64 a word >= p raises the same flag.
+ *   lf_witness_wire_header (host only, no context): every format check.
+ *     LF_ERR_INCORRECT_LENGTH: len < 32, or len != 32 + N d bits / 8 (computed without
+ *     overflow); LF_ERR_INVALID_ARG: wrong magic, bits not in {16, 32, 64}, reserved != 0,
+ *     L < 1, N not a multiple of L; LF_ERR_UNSUPPORTED_RING: an unsupported d.
+ *   lf_witness_serialize: reads only w->f_coeff (device memory). bits = 0: the narrowest
+ *     width, so a witness has one canonical encoding. out == NULL (or too small:
+ *     LF_ERR_INCORRECT_LENGTH) still returns the size. An explicit width that does not fit:
+ *     LF_ERR_DECOMPOSITION_OVERFLOW.
+ *   lf_witness_deserialize (synchronous): fills the caller's three device buffers from any
+ *     valid width. Calls lf_witness_wire_header first and launches nothing on malformed
+ *     input; LF_ERR_INVALID_ARG also for d or L different from pr, N different from the
+ *     argument, and a 64-bit word >= p. */
+size_t lf_witness_packed_len(int d, size_t N, int bits);
+int lf_dev_witness_bits(lf_ctx *ctx, int d, const uint64_t *f_coeff, size_t N, int *bits, uint64_t *norm);
+int lf_dev_witness_pack(lf_ctx *ctx, int d, const uint64_t *f_coeff, size_t N, int bits, void *packed);
+int lf_dev_witness_unpack(lf_ctx *ctx, const lf_params *pr, const void *packed, int bits, size_t N,
+                          uint64_t *f_coeff, uint64_t *f, uint64_t *w_ccs);
+int lf_witness_wire_header(const uint8_t *in, size_t len, int *d, int *L, int *bits, size_t *N);
+
 /* ------------------------------------------------------------ fold() end to end
  * zk_latticefold_prove (zkvm/src/zk_latticefold.rs:37-102), what fold()
  * (zkvm/src/main.rs:369-404) runs with a fresh Poseidon2 transcript:
@@ -856,6 +906,11 @@ typedef struct {
   uint64_t *f;       /* N = W L NTT elements */
   uint64_t *f_coeff; /* N coefficient-form elements */
 } lf_witness;
+/* the witness's wire bytes (format and codes: "witness wire format" above) */
+int lf_witness_serialize(lf_ctx *ctx, const lf_params *pr, const lf_witness *w, size_t N, int bits,
+                         uint8_t *out, size_t cap, size_t *len);
+int lf_witness_deserialize(lf_ctx *ctx, const lf_params *pr, const uint8_t *in, size_t len,
+                           const lf_witness *out, size_t N);
 typedef struct {
   uint64_t *r;   /* s */
   uint64_t *v;   /* tau */

@@ -215,6 +215,39 @@ class Context:
         self.check(self.lib.lf_witness_from_f(self.h, C.byref(params), _ptr(x), N, _ptr(fc), _ptr(w), repr))
         return fc, w
 
+    def witness_from_f_coeff(self, f_coeff, params: LfParams, repr: int = REPR_CANONICAL):
+        """Witness::from_f_coeff on host arrays: f_coeff [N] -> (f [N], w_ccs [N / L])"""
+        x = _u64(f_coeff)
+        d, L = params.d, params.L
+        N = x.size // d
+        f = np.empty(N * d, np.uint64)
+        w = np.empty((N // L) * d, np.uint64)
+        self.check(self.lib.lf_witness_from_f_coeff(self.h, C.byref(params), _ptr(x), N, _ptr(f), _ptr(w), repr))
+        return f, w
+
+    def dev_witness_from_f_coeff(self, params: LfParams, f_coeff, N: int, f, w_ccs):
+        """Witness::from_f_coeff on device buffers (asynchronous): f = CRT(f_coeff), w_ccs = recompose(f)"""
+        self.check(self.lib.lf_dev_witness_from_f_coeff(self.h, C.byref(params), _dptr(f_coeff), N, _dptr(f),
+                                                        _dptr(w_ccs)))
+
+    def dev_witness_bits(self, d: int, f_coeff, N: int) -> tuple[int, int]:
+        """(the narrowest packed width that holds every coefficient: 16, 32 or 64; the l_inf norm on
+        signed representatives) of a device f_coeff; synchronises (lf_dev_witness_bits)"""
+        bits, norm = C.c_int(0), C.c_uint64(0)
+        self.check(self.lib.lf_dev_witness_bits(self.h, d, _dptr(f_coeff), N, C.byref(bits), C.byref(norm)))
+        return bits.value, norm.value
+
+    def dev_witness_pack(self, d: int, f_coeff, N: int, bits: int, packed):
+        """f_coeff -> N d centred integers of `bits` bits (asynchronous; a coefficient that does not
+        fit makes the next sync() raise LF_ERR_DECOMPOSITION_OVERFLOW)"""
+        self.check(self.lib.lf_dev_witness_pack(self.h, d, _dptr(f_coeff), N, bits, _dptr(packed)))
+
+    def dev_witness_unpack(self, params: LfParams, packed, bits: int, N: int, f_coeff, f=None, w_ccs=None):
+        """the packed words -> f_coeff and, unless both are None, f and w_ccs (asynchronous)"""
+        self.check(self.lib.lf_dev_witness_unpack(self.h, C.byref(params), _dptr(packed), bits, N, _dptr(f_coeff),
+                                                  None if f is None else _dptr(f),
+                                                  None if w_ccs is None else _dptr(w_ccs)))
+
     def dev_decompose_witness(self, params: LfParams, f_coeff, N: int, f_coeff_k, f_k, w_ccs_k):
         """decompose_witness on device buffers: f_coeff [N] -> [K][N], [K][N], [K][N / L]"""
         self.check(self.lib.lf_dev_decompose_witness(self.h, C.byref(params), _dptr(f_coeff), N, _dptr(f_coeff_k),

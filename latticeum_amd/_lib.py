@@ -121,6 +121,7 @@ SIGNATURES = {
     "lf_ajtai_commit": (I, [VP, VP, VP, SZ, VP, I]),
     "lf_witness_from_w_ccs": (I, [VP, C.POINTER(LfParams), VP, SZ, VP, VP, I]),
     "lf_witness_from_f": (I, [VP, C.POINTER(LfParams), VP, SZ, VP, VP, I]),
+    "lf_witness_from_f_coeff": (I, [VP, C.POINTER(LfParams), VP, SZ, VP, VP, I]),
     "lf_decompose_witness": (I, [VP, C.POINTER(LfParams), VP, SZ, VP, VP, VP, I]),
     "lf_commit": (I, [VP, VP, C.POINTER(LfParams), VP, SZ, SZ, VP, VP, VP, I]),
     "lf_fold_hot": (I, [VP, VP, C.POINTER(LfParams), VP, VP, VP, VP, SZ, VP, VP, VP, VP, VP, VP, I]),
@@ -133,6 +134,7 @@ SIGNATURES = {
     "lf_dev_from_montgomery": (I, [VP, VP, SZ]),
     "lf_dev_witness_from_w_ccs": (I, [VP, C.POINTER(LfParams), VP, SZ, VP, VP]),
     "lf_dev_witness_from_f": (I, [VP, C.POINTER(LfParams), VP, SZ, VP, VP]),
+    "lf_dev_witness_from_f_coeff": (I, [VP, C.POINTER(LfParams), VP, SZ, VP, VP]),
     "lf_dev_decompose_witness": (I, [VP, C.POINTER(LfParams), VP, SZ, VP, VP, VP]),
     "lf_dev_ajtai_commit": (I, [VP, VP, C.POINTER(VP), I, VP]),
     "lf_dev_commit_y0": (I, [VP, C.POINTER(LfParams), VP, VP, SZ]),
@@ -191,6 +193,13 @@ SIGNATURES = {
     "lf_memtree_audit": (I, [VP, SZ, SZ, VP, VP, VP, SZ, VP, VP, VP, VP, C.POINTER(C.c_int64), C.POINTER(I)]),
     "lf_lcccs_serialize": (I, [C.POINTER(LfLcccs), I, VP, SZ, C.POINTER(SZ)]),
     "lf_lcccs_deserialize": (I, [VP, SZ, I, I, VP, SZ, C.POINTER(LfLcccs)]),
+    "lf_witness_packed_len": (SZ, [I, SZ, I]),
+    "lf_dev_witness_bits": (I, [VP, I, VP, SZ, C.POINTER(I), C.POINTER(U64)]),
+    "lf_dev_witness_pack": (I, [VP, I, VP, SZ, I, VP]),
+    "lf_dev_witness_unpack": (I, [VP, C.POINTER(LfParams), VP, I, SZ, VP, VP, VP]),
+    "lf_witness_wire_header": (I, [VP, SZ, C.POINTER(I), C.POINTER(I), C.POINTER(I), C.POINTER(SZ)]),
+    "lf_witness_serialize": (I, [VP, C.POINTER(LfParams), C.POINTER(LfWitness), SZ, I, VP, SZ, C.POINTER(SZ)]),
+    "lf_witness_deserialize": (I, [VP, C.POINTER(LfParams), VP, SZ, C.POINTER(LfWitness), SZ]),
     "lf_lfproof_serialize": (I, [C.POINTER(LfLfproof), I, VP, SZ, C.POINTER(SZ)]),
     "lf_dev_eq_table": (I, [VP, I, VP, I, VP]),
     "lf_dev_get_fhat": (I, [VP, I, VP, SZ, I, VP]),

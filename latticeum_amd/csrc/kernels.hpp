@@ -300,6 +300,25 @@ hipError_t from_f_n4k(const uint64_t *f, size_t W, int lb, int L, uint64_t *f_co
 hipError_t from_w_ccs_n4k(const uint64_t *w_ccs, size_t W, int lb, int L, uint64_t *f_coeff, uint64_t *f,
                           const ring::NegaTables &fwd, const ring::NegaTables &inv, int *err, hipStream_t st);
 
+// ---------------------------------------------------------------- Witness::from_f_coeff and the packed witness (witness_pack.hip)
+// f = CRT(f_coeff) over N elements, w_ccs = recompose(f) over N / L, at every ring. src holds
+// the N d coefficients as the words of source `kind` (wsrc.hpp WitnessSrc: canonical u64, or a
+// packed payload's i16 / i32 / checked u64); fc_out (may be null) gets them in canonical form
+// from the same launch. err: raised by a checked u64 word >= p.
+hipError_t from_fcoeff(const void *src, int kind, size_t N, int d, int lb, int L, uint64_t *fc_out, uint64_t *f,
+                       uint64_t *w_ccs, const ring::NegaTables &fwd, int *err, hipStream_t st);
+// its d = 1024 (a source other than plain f_coeff) and d = 4096 forms, on the register-resident 32 x 32 NTT
+hipError_t from_fcoeff_src_n32(const void *src, int kind, size_t W, int lb, int L, uint64_t *fc_out, uint64_t *f,
+                               uint64_t *w_ccs, const ring::NegaTables &fwd, int *err, hipStream_t st);
+hipError_t from_fcoeff_n4k(const void *src, int kind, size_t W, int lb, int L, uint64_t *fc_out, uint64_t *f,
+                           uint64_t *w_ccs, const ring::NegaTables &fwd, int *err, hipStream_t st);
+// n coefficients (a multiple of 8; both pointers 16-byte aligned) to / from the packed words;
+// pack raises err for a coefficient outside the width, decode for a u64 word >= p
+hipError_t witness_pack(const uint64_t *fc, size_t n, int bits, void *out, int *err, hipStream_t st);
+hipError_t witness_decode(const void *in, int kind, size_t n, uint64_t *fc, int *err, hipStream_t st);
+// out[0], out[1] = how many centred coefficients lie outside the i16 / the i32 range
+hipError_t witness_range(const uint64_t *fc, size_t n, uint64_t *out, hipStream_t st);
+
 // ---------------------------------------------------------------- sumcheck (sumcheck.hip)
 // the multisets S_i of a CCS (linearization polynomial), by value as a kernel argument
 constexpr int LF_MAX_MULTISETS = 64, LF_MAX_S = 512;

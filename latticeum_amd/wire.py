@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import (LfCcsDesc, LfDecompositionProof, LfLcccs, LfLfproof, LfLfproofMut, LfParams, LfRingSlice,
-                   load)
+                   LfWitness, load)
 
 REPR_CANONICAL, REPR_MONTGOMERY = 0, 1
 
@@ -131,3 +131,56 @@ def deserialize_lfproof(data: bytes, params: LfParams, t: int, m: int, l: int, d
         v = getattr(out, k)
         res[k] = take(v) if k not in ("u_s", "v_s", "x_s", "y_s") else [take(v[0]), take(v[1])]
     return res
+
+
+# ---------------------------------------------------------------- the witness (lf.h "witness wire format")
+def _dev(t) -> int:
+    return t if isinstance(t, int) else t.data_ptr()
+
+
+def _lf_witness(w: dict) -> LfWitness:
+    return LfWitness(_dev(w["w_ccs"]), _dev(w["f"]), _dev(w["f_coeff"]))
+
+
+def _ctx_error(ctx, what: str, rc: int) -> LfError:
+    msg = ctx.lib.lf_ctx_last_error(ctx.h).decode()
+    return LfError(f"{what} rc={rc}" + (f": {msg}" if msg else ""), rc)
+
+
+def witness_wire_header(data: bytes) -> dict:
+    """lf_witness_wire_header: {d, L, bits, N} of a witness's wire bytes after every format
+    check (host only); LfError with the status in .code otherwise"""
+    raw = np.frombuffer(bytes(data), np.uint8).copy() if len(data) else np.zeros(1, np.uint8)
+    d, L, bits, N = C.c_int(), C.c_int(), C.c_int(), C.c_size_t()
+    rc = load().lf_witness_wire_header(raw.ctypes.data_as(C.c_void_p), len(data), C.byref(d), C.byref(L),
+                                       C.byref(bits), C.byref(N))
+    if rc:
+        raise LfError(f"witness header rc={rc}", rc)
+    return {"d": d.value, "L": L.value, "bits": bits.value, "N": N.value}
+
+
+def serialize_witness(ctx, params: LfParams, witness: dict, N: int, bits: int = 0) -> bytes:
+    """the wire bytes of a device witness {w_ccs, f, f_coeff} (only f_coeff is read);
+    bits = 0: the narrowest of 16, 32, 64 that holds every coefficient"""
+    lib, w = load(), _lf_witness(witness)
+    n = C.c_size_t()
+    rc = lib.lf_witness_serialize(ctx.h, C.byref(params), C.byref(w), N, bits, None, 0, C.byref(n))
+    if rc != 7:
+        raise _ctx_error(ctx, "witness serialize", rc)
+    buf = np.empty(n.value, np.uint8)
+    rc = lib.lf_witness_serialize(ctx.h, C.byref(params), C.byref(w), N, bits, buf.ctypes.data_as(C.c_void_p),
+                                  buf.size, C.byref(n))
+    if rc:
+        raise _ctx_error(ctx, "witness serialize", rc)
+    return buf[:n.value].tobytes()
+
+
+def deserialize_witness(ctx, params: LfParams, data: bytes, witness: dict, N: int) -> None:
+    """fills the device buffers {w_ccs, f, f_coeff} from a witness's wire bytes (synchronous);
+    LfError with the status in .code for bytes that are malformed or of another shape"""
+    raw = np.frombuffer(bytes(data), np.uint8).copy() if len(data) else np.zeros(1, np.uint8)
+    w = _lf_witness(witness)
+    rc = load().lf_witness_deserialize(ctx.h, C.byref(params), raw.ctypes.data_as(C.c_void_p), len(data),
+                                       C.byref(w), N)
+    if rc:
+        raise _ctx_error(ctx, "witness deserialize", rc)

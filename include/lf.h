@@ -481,6 +481,14 @@ int lf_dev_gl_probe(lf_ctx *ctx, int op, const uint64_t *a, const uint64_t *b, i
  * nothing and leaves the decomposition-overflow state to lf_ctx_sync. In a batch every step's
  * context reports its own step. */
 int lf_ctx_fold_flag(lf_ctx *ctx, int *out);
+/* test aid beside lf_ctx_fold_flag: the level of the Karatsuba split of the Toeplitz
+ * products that the step's d = 1024 coefficient-form fold ran at. The device picks it per
+ * step with no host synchronisation: the highest level that is built (1) whose split tables
+ * all fit i8, capped by the environment variable LATTICEUM_AMD_FOLD_KARA (0 or 1; read at
+ * every step), and 0 (the dense product) otherwise and whenever lf_ctx_fold_flag gives 1.
+ * *out = -1 when the step took another path. Every level gives the same bits. It waits for
+ * the context's stream and launches nothing. */
+int lf_ctx_fold_level(lf_ctx *ctx, int *out);
 /* test aid: the launch plan of one sumcheck round over `half` = 2^(nv-1-i) points (round i of
  * an nv-variable prove), as the round launchers themselves decide it (they call the same
  * function). kind: the folding round, the unsplit linearization round (lf_sumcheck_prove and

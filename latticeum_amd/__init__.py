@@ -133,6 +133,13 @@ class Context:
         self.check(self.lib.lf_ctx_fold_flag(self.h, C.byref(out)))
         return out.value
 
+    def fold_level(self) -> int:
+        """test aid (lf_ctx_fold_level): waits for the stream; the Karatsuba level (0 = the dense
+        product) the last fold step's d = 1024 coefficient-form fold ran at, -1 on other paths"""
+        out = C.c_int()
+        self.check(self.lib.lf_ctx_fold_level(self.h, C.byref(out)))
+        return out.value
+
     def use_cu_mask(self, cus):
         """run this context's work on a stream of its own restricted to the
         compute units `cus` (iterable of CU indices); lf_stream_create_cu_mask"""

@@ -145,6 +145,7 @@ SIGNATURES = {
     "lf_dev_poseidon2_permute_rounds": (I, [VP, VP, SZ, I]),
     "lf_dev_gl_probe": (I, [VP, I, VP, VP, I, I, VP, SZ]),
     "lf_ctx_fold_flag": (I, [VP, C.POINTER(I)]),
+    "lf_ctx_fold_level": (I, [VP, C.POINTER(I)]),
     "lf_sumcheck_round_plan": (I, [I, SZ, I, I, C.POINTER(I * 8)]),
     "lf_sumcheck_dot_plan": (I, [I, SZ, C.POINTER(I * 4)]),
     "lf_dev_fhat_lincomb_digits": (I, [VP, I, VP, SZ, SZ, I, I, VP, VP]),

@@ -70,6 +70,7 @@ struct lf_ctx {
   size_t fpart_elems = 0;
   size_t faux_elems = 0;
   long fold_flag_at = -1;       // the last fold_finish's not-short flag: its u64 index in faux, -1 = a path without one
+  bool fold_has_level = false;  // that u64's second int is the Karatsuba level that ran (lf_ctx_fold_level)
   uint64_t *sink = nullptr;     // 32 KiB row the fused decompositions store work past the end into
   uint8_t *dead = nullptr;      // dead-unit flags of the operand rows (lfk::DeadUnits) [2 nch][32]
   size_t dead_elems = 0;

@@ -353,6 +353,7 @@ int fold_finish(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, int lb, int 
   LF_HIP(c, lfk::y0_cm0(b->acc_cm, cm_i, b->y[0], b->y[1], b->rho, kappa, d, lbs, K, b->cm0, c->cur, cm1_out));
   const StepState &st = c->step;
   c->fold_flag_at = -1;  // lf_ctx_fold_flag: set below where the path has a flag
+  c->fold_has_level = false;
   // the f_k rows of both sides, for the NTT-form fold
   auto fk_rows = [&] {
     lfk::VecPtrs fx{};
@@ -368,7 +369,9 @@ int fold_finish(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, int lb, int 
     // turns those kernels off and the NTT-form fold and from_f on.
     case FoldPath::Coeff1024:
     case FoldPath::Coeff1024Rows: {
-      const size_t tab_u64 = ((size_t)nw * lfk::FOLD_RT + 7) / 8, aux = (size_t)nw * 1024 + tab_u64 + 1;
+      // the last u64 of aux: the not-short flag and the Karatsuba level that ran (two ints)
+      const size_t tab_u64 = (lfk::fold_tab_bytes(nw) + 7) / 8, aux = (size_t)nw * 1024 + tab_u64 + 1;
+      const int kara = lfk::fold_kara_cap();
       // the digit keys [2 N][K][64] u32, then each column's plane mask [2 N] u32
       LF_TRY(grow(c, c->fkeys, c->fkeys_elems, 2 * N * (size_t)K * 64 + 2 * N));
       uint32_t *nz = c->fkeys + 2 * N * (size_t)K * 64;
@@ -377,11 +380,12 @@ int fold_finish(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, int lb, int 
       uint8_t *tab = reinterpret_cast<uint8_t *>(c->faux + (size_t)nw * 1024);
       int *bad = reinterpret_cast<int *>(c->faux + aux - 1);
       c->fold_flag_at = (long)(aux - 1);
+      c->fold_has_level = true;
       {
         PhaseTimer pt(c, LF_PHASE_FOLD);
         for (int s = 0; s < 2; s++)
           LF_HIP(c, lfk::fold_keys(st.smg_side[s], N, K, c->fkeys + (size_t)s * N * K * 64, c->cur, nz + (size_t)s * N));
-        LF_HIP(c, lfk::fold_rho_tables(b->rho, nw, rc, tab, bad, t->inv, c->d_sync, c->cur));
+        LF_HIP(c, lfk::fold_rho_tables(b->rho, nw, rc, tab, bad, t->inv, c->d_sync, c->cur, kara));
         const int ks_n = lfk::fold_coeff_splits(N, K, c->ncu);
         if (ks_n > 1) LF_TRY(grow(c, c->fpart, c->fpart_elems, (size_t)ks_n * N * 1024));
         // packed planes: the fallback (f_0 in NTT form from the operand rows) runs
@@ -389,7 +393,7 @@ int fold_finish(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, int lb, int 
         const bool in_launch = st.path == FoldPath::Coeff1024Rows;
         const lfk::FoldFallback fb{c->frag, aj->geom.nch, aj->geom.Lp, aj->geom.Wp, st.fold_rows, b->rho, b->f0};
         LF_HIP(c, lfk::fold_coeff(c->fkeys, tab, bad, N, K, b->f0_coeff, c->ncu, c->cur,
-                                  ks_n > 1 ? c->fpart : nullptr, in_launch ? &fb : nullptr, L, nz));
+                                  ks_n > 1 ? c->fpart : nullptr, in_launch ? &fb : nullptr, L, nz, kara));
         if (!in_launch) LF_HIP(c, lfk::fold(b->rho, fk_rows(), nw, N, d, b->f0, c->cur, bad));
       }
       // f_0 and w_ccs from f_0's coefficients, or (flag set) Witness::from_f of the

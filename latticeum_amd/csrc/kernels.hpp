@@ -231,11 +231,22 @@ hipError_t expand_smp2(const uint32_t *smg, size_t N, int d, int K, uint64_t *fc
 // [nw][FOLD_RT] bytes, *bad = 1 if a coefficient is outside [-127, 127];
 // fold_coeff writes f0c = the canonical coefficients of sum_i rho_i f_i unless *bad
 constexpr int FOLD_RT = 2080;
+// The Karatsuba split of the Toeplitz product (fold_coeff.hip's header): after the
+// nw dense tables tab holds the level-1 tables [nw][3][FOLD_RT1] bytes (the reversed
+// generators of T1, T2 - T1 and T1 + T2), and bad[1] is the level the step's
+// fold_coeff runs at: min(kara_cap, the highest level whose every table entry fits
+// i8), 0 when *bad
+constexpr int FOLD_RT1 = 1040;
+constexpr int FOLD_KARA_MAX = 1;  // the highest level that is built
+constexpr size_t fold_tab_bytes(int nw) { return (size_t)nw * (FOLD_RT + 3 * FOLD_RT1); }
+// the level cap of a step: LATTICEUM_AMD_FOLD_KARA = 0 .. FOLD_KARA_MAX (default: FOLD_KARA_MAX)
+int fold_kara_cap();
 // nz (may be null): [ncol] u32, bit k = plane k of the column has a nonzero digit
 hipError_t fold_keys(const uint32_t *smg, size_t ncol, int K, uint32_t *keys, hipStream_t st, uint32_t *nz = nullptr);
-// sync: two ints, zero before the first launch; every launch leaves them zero
+// sync: two ints, zero before the first launch; every launch leaves them zero.
+// tab: fold_tab_bytes(nw) bytes; bad: two ints (the not-short flag, the level)
 hipError_t fold_rho_tables(const uint64_t *rho, int nw, uint64_t *rc, uint8_t *tab, int *bad,
-                           const ring::NegaTables &inv, int *sync, hipStream_t st);
+                           const ring::NegaTables &inv, int *sync, hipStream_t st, int kara_cap = 0);
 // part: fold_coeff_splits() N 1024 int32 of scratch for the witness-split partial
 // sums when there are few elements (or null: no split)
 int fold_coeff_splits(size_t N, int K, int ncu);
@@ -250,10 +261,11 @@ struct FoldFallback {
   uint64_t *f0;
 };
 // L: the gadget length (elements g L + l; the tiles are limb-pure); nz: both sides'
-// plane masks [2 N] from fold_keys (null: every plane is multiplied)
+// plane masks [2 N] from fold_keys (null: every plane is multiplied); kara_cap: what
+// fold_rho_tables was given (tab and bad are its outputs)
 hipError_t fold_coeff(const uint32_t *keys, const uint8_t *tab, const int *bad, size_t N, int K, uint64_t *f0c,
                       int ncu, hipStream_t st, int32_t *part = nullptr, const FoldFallback *fb = nullptr, int L = 1,
-                      const uint32_t *nz = nullptr);
+                      const uint32_t *nz = nullptr, int kara_cap = 0);
 // Witness::from_f given f's coefficients: f = NTT(f_coeff), w_ccs = recompose(f); gate: as
 // fold_coeff. With inv, a set gate runs Witness::from_f of f instead (f_coeff = ICRT(f),
 // w_ccs = recompose(f)) in the same launch: the NTT-form fold's fallback path

@@ -466,6 +466,20 @@ int lf_ctx_fold_flag(lf_ctx *c, int *out) {
   return LF_OK;
 }
 
+// test aid: the Karatsuba level the last fold_finish's d = 1024 coefficient-form fold ran
+// at (the int beside the not-short flag; 0 when that flag is set); -1 on the paths without one
+int lf_ctx_fold_level(lf_ctx *c, int *out) {
+  DevGuard g(c);
+  if (!c || !out) return LF_ERR_INVALID_ARG;
+  LF_HIP(c, hipStreamSynchronize(c->cur));
+  *out = -1;
+  if (!c->fold_has_level || c->fold_flag_at < 0 || !c->faux || (size_t)c->fold_flag_at >= c->faux_elems) return LF_OK;
+  int w[2] = {0, 0};
+  LF_HIP(c, hipMemcpy(w, c->faux + c->fold_flag_at, sizeof w, hipMemcpyDeviceToHost));
+  *out = w[1];  // 0 when the flag is set
+  return LF_OK;
+}
+
 int lf_ctx_reserve(lf_ctx *c, size_t kappa, size_t ncols, int d, int nvec) {
   DevGuard g(c);
   if (!c || !ring_ok(d) || nvec < 1 || nvec > LF_MAX_VECS) return LF_ERR_INVALID_ARG;

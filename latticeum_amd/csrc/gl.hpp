@@ -70,6 +70,36 @@ LF_HD uint64_t from_x_y32(int64_t X, int64_t Y) {
   return canon(t + (uint64_t)((int64_t)k * (int64_t)EPS));
 }
 
+LF_HD uint64_t mul_pow2(uint64_t a, int s);
+
+// The signed 32-bit limbs of M_g = 2^(24g) m (mod p), g in {0, 1, 2}, any u64 m: M_g = lo +
+// 2^32 hi for the representative in [-(p + 1)/2, (p - 1)/2). Every integer of
+// [-2^63 - 2^31, 2^63 - 2^31) is lo + 2^32 hi with both limbs in i32 exactly one way, and
+// (p - 1)/2 = 2^63 - 2^31 is the first one past it, so that residue takes its negative
+// representative. |lo|, |hi| <= 2^31.
+LF_HD void mid_limbs(uint64_t m, int g, int32_t &lo, int32_t &hi) {
+  const uint64_t c = canon(mul_pow2(m, 24 * g));
+  const int64_t M = (int64_t)(c >= (P - 1) / 2 ? c - P : c);
+  lo = (int32_t)(uint32_t)(uint64_t)M;
+  hi = (int32_t)((M - (int64_t)lo) >> 32);  // |M - lo| <= 2^63: no wrap
+}
+
+// Y m (mod p), canonical, for Y = G0 + 2^24 G1 + 2^48 G2 and the limbs of mid_limbs(m, g):
+// Y m == sum_g G_g M_g = X + 2^32 H with X = sum_g G_g lo_g, H = sum_g G_g hi_g, six signed
+// 32 x 32 multiply-adds (v_mad_i64_i32). For the i8-MFMA byte sums |D_t| <= 2^12 grouped by
+// three (G0 = D0 + 2^8 D1 + 2^16 D2, G1 likewise from D3..D5, G2 = D6 + 2^8 D7): |G0|, |G1| <=
+// 2^12 (1 + 2^8 + 2^16) < 2^28.01, |G2| < 2^20.01, so |X|, |H| <= 2^31 (2 2^28.01 + 2^20.01) <
+// 2^60.02, inside from_x_y32's 2^62. (|D_t| <= 2^14, the d = 4096 sums, gives < 2^62.02: not
+// covered.)
+LF_HD uint64_t mul_mid3(const int32_t G[3], const int32_t lo[3], const int32_t hi[3]) {
+  int64_t X = (int64_t)G[0] * lo[0], H = (int64_t)G[0] * hi[0];
+  X += (int64_t)G[1] * lo[1];
+  H += (int64_t)G[1] * hi[1];
+  X += (int64_t)G[2] * lo[2];
+  H += (int64_t)G[2] * hi[2];
+  return from_x_y32(X, H);
+}
+
 // 64x64 -> 128 from four 32x32 -> 64 multiply-adds (v_mad_u64_u32 each; no
 // intermediate sum overflows: (2^32-1)^2 + 2 (2^32-1) = 2^64 - 1)
 LF_HD void mul_wide(uint64_t a, uint64_t b, uint64_t &lo, uint64_t &hi) {

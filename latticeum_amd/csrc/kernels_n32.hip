@@ -539,8 +539,14 @@ __global__ void __launch_bounds__(256, 1) k_decompose_n32(const uint64_t *f_coef
 // The group's coefficients come pre-packed as sign|magnitude words (k_pack_sm;
 // digitpack.hpp, d = 1024), read back per (k, l), one plane ahead.
 constexpr int FD_WAVES = 8;
-constexpr int FD_SROW = 17;  // staging row stride in u64 (16 columns + pad: conflict-free)
+// Staging row stride in u64: the 16 columns and no pad (the pad's 8 KiB went to the middle
+// factors' limb tables). Column c of slot s sits at s * 16 + (c ^ ((s >> 1) & 15)): the u64 bank
+// is 16 (s & 1) + (c ^ ((s >> 1) & 15)), distinct over any 32 consecutive slots of one column
+// (the writes) and of one row position (the reads), as with the padded stride.
+constexpr int FD_SROW = 16;
 constexpr int FD_S_U64 = D * FD_SROW;
+__device__ __forceinline__ int fd_s_index(int slot, int col) { return slot * FD_SROW + (col ^ ((slot >> 1) & 15)); }
+constexpr int MID3_ROWS = 31;  // rows j1 = 1 .. 31 of each limb table (row 0 is the constant 2^(24g))
 
 // four packed words per thread (t0 = 4 * thread): 2 x 32 contiguous bytes in,
 // one 16-B store out
@@ -575,8 +581,7 @@ __global__ void k_pack_sm(FusedSides sd, size_t N, int K, int *err) {
 // v_mfma_i32_32x32x32_i8 per byte plane (|sum| <= 32 * 128) replaces the two
 // integer and three field levels of neg_ct32 per lane. Lane (r, h) holds
 // Z_t[r][16 h + j] and B[16 h + j][r] (j < 16) and gets D[m1][j1 = r] for
-// m1 = (i & 3) + 8 (i >> 2) + 4 h in register i; Y = Q0 + Q1 2^32 with Q0 =
-// sum_{t < 4} 2^(8t) D_t, Q1 = sum_{t >= 4} 2^(8(t-4)) D_t (|Q| < 2^37). A wave
+// m1 = (i & 3) + 8 (i >> 2) + 4 h in register i; Y = sum_t 2^(8t) D_t. A wave
 // does both of its halves' elements (16 products), so the transpose into the
 // second stage's layout stays inside the wave's own LDS tiles.
 __device__ __forceinline__ v4i mx_digits(const uint32_t *w8, int kb) {
@@ -599,71 +604,77 @@ __device__ __forceinline__ v4i az_piece(const int8_t *azl, int t, int r, int h) 
   return *reinterpret_cast<const v4i *>(azl + (t * 32 + r) * 32 + 16 * h);
 }
 // Transposed: digits as the A operand (rows j1, K = j2), Z as B (K = j2, columns
-// m1), so lane (r, h) gets Y[j1][m1 = r] for j1 = (i & 3) + 8 (i >> 2) + 4 h in
+// m1), so lane (r, h) gets D_t[j1][m1 = r] for j1 = (i & 3) + 8 (i >> 2) + 4 h in
 // register i -- the rows of column m1 = r that stage 2 wants in lane r, split
-// between the two halves. The middle factors come after both elements
-// (mid2_apply: mid2[j1][m1] = psi^((2 m1 + 1) j1), staged by mid2_stage).
-__device__ __forceinline__ void mx_stage1_t(const int8_t *azl, const uint32_t *w8, int kb, uint64_t *y, int r, int h) {
+// between the two halves. Y = sum_t 2^(8t) D_t is never formed: the byte sums
+// (|D_t| <= 32 * 128) are grouped by three in i32, G0 = D0 + 2^8 D1 + 2^16 D2,
+// G1 the same of D3..D5, G2 = D6 + 2^8 D7 (|G0|, |G1| < 2^28.01, |G2| < 2^20.01),
+// so Y = G0 + 2^24 G1 + 2^48 G2, and the middle factors multiply the groups
+// (mid3_apply) after both elements.
+__device__ __forceinline__ void mx_stage1_t(const int8_t *azl, const uint32_t *w8, int kb, int32_t (*G)[16], int r, int h) {
   const v4i b = mx_digits(w8, kb);
-  // Q = sum_t 2^(8t) D_t over 4 planes, two planes at a time (|partial| < 2^21 in int32)
-  auto quarter = [&](int t0, int64_t *q) {
-    v16i a0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(b, az_piece(azl, t0, r, h), (v16i){0}, 0, 0, 0);
-    v16i a1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(b, az_piece(azl, t0 + 1, r, h), (v16i){0}, 0, 0, 0);
-    int32_t p[16];
+  auto prod = [&](int t) { return __builtin_amdgcn_mfma_i32_32x32x32_i8(b, az_piece(azl, t, r, h), (v16i){0}, 0, 0, 0); };
 #pragma unroll
-    for (int i = 0; i < 16; i++) p[i] = a0[i] + a1[i] * 256;
-    a0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(b, az_piece(azl, t0 + 2, r, h), (v16i){0}, 0, 0, 0);
-    a1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(b, az_piece(azl, t0 + 3, r, h), (v16i){0}, 0, 0, 0);
+  for (int g = 0; g < 3; g++) {
+    const v16i a0 = prod(3 * g), a1 = prod(3 * g + 1);
 #pragma unroll
-    for (int i = 0; i < 16; i++) q[i] = (int64_t)(p[i] + a0[i] * 65536) + (int64_t)a1[i] * (1ll << 24);
-  };
-  int64_t q0[16], q1[16];
-  quarter(0, q0);
-  quarter(4, q1);
+    for (int i = 0; i < 16; i++) G[g][i] = a0[i] + a1[i] * 256;
+    if (g < 2) {
+      const v16i a2 = prod(3 * g + 2);
 #pragma unroll
-  for (int i = 0; i < 16; i++) {
-    // Y = Q0 + Q1 2^32 == A + (Q1l + Q1h) 2^32 with Q1 = Q1h 2^32 + Q1l, A = Q0 - Q1h
-    // (2^64 == 2^32 - 1); = A.lo + T 2^32 with T = A.hi + Q1l + Q1h in (-2^7, 2^32 + 2^7),
-    // = U + th 2^64 == U + th EPS, U = T.lo:A.lo, th = T >> 32 in {-1, 0, 1} (no wrap:
-    // th = 1 leaves U < 2^39, th = -1 U > EPS). Any u64 is a valid gl::mul input.
-    const int64_t q1h = q1[i] >> 32;
-    const int64_t A = q0[i] - q1h;
-    const int64_t T = (A >> 32) + (int64_t)(uint32_t)q1[i] + q1h;
-    const uint64_t U = ((uint64_t)T << 32) | (uint32_t)A;
-    const uint64_t yv = U + (uint64_t)((T >> 32) * (int64_t)gl::EPS);
-    y[i] = yv;  // the middle factors follow for both elements at once (mid2_apply)
+      for (int i = 0; i < 16; i++) G[g][i] += a2[i] * 65536;
+    }
   }
 }
-// y0, y1 *= mid2[j1][m1 = r] with one table read per row for both elements
-__device__ __forceinline__ void mid2_apply(const uint64_t *mid2, uint64_t *y0, uint64_t *y1, int r, int h) {
+// y_e = Y_e psi^((2 m1 + 1) j1), m1 = r, for both elements from their grouped sums,
+// with one read of the row's three limb pairs for both (per element: the same
+// 2 spilled registers, 6 more VALU and 26 more LDS reads per body): gl::mul_mid3's
+// six signed 32 x 32 multiply-adds and one fold per value. Row j1 = 0 (register 0
+// of the lower half) is the constants 2^(24g) and is not stored.
+__device__ __forceinline__ void mid3_apply(const int2 *mid3, const int32_t (*G0)[16], const int32_t (*G1)[16], uint64_t *y0,
+                                           uint64_t *y1, int r, int h) {
 #pragma unroll
   for (int i = 0; i < 16; i++) {
     const int j1 = (i & 3) + 8 * (i >> 2) + 4 * h;
-    const uint64_t m = mid2[j1 * 32 + r];
-    y0[i] = gl::mul(y0[i], m);
-    y1[i] = gl::mul(y1[i], m);
+    int32_t lo[3], hi[3];
+#pragma unroll
+    for (int g = 0; g < 3; g++) {
+      // register 0: the lower half reads the upper half's row (j1 = 4) and drops it
+      const int2 m = mid3[g * MID3_ROWS * 32 + (i ? j1 - 1 : 3) * 32 + r];
+      lo[g] = m.x, hi[g] = m.y;
+      if (i == 0 && h == 0) lo[g] = g == 1 ? 1 << 24 : g == 0, hi[g] = g == 2 ? 1 << 16 : 0;
+    }
+    const int32_t g0[3] = {G0[0][i], G0[1][i], G0[2][i]}, g1[3] = {G1[0][i], G1[1][i], G1[2][i]};
+    y0[i] = gl::mul_mid3(g0, lo, hi);
+    y1[i] = gl::mul_mid3(g1, lo, hi);
   }
 }
-// mid2[j1][m1] = psi^((2 m1 + 1) j1) from the launcher's table mid[j1][i'] =
-// psi^((2 brv5(i') + 1) j1) (n32::stage_mid's source layout)
-__device__ __forceinline__ void mid2_stage(uint64_t *mid2, const uint64_t *mid) {
-  for (int q = threadIdx.x; q < n32::MID_U64; q += blockDim.x) mid2[q] = mid[(q & ~31) | n32::brv5(q & 31)];
+// mid3[g][j1 - 1][m1] = the limbs (lo, hi) of 2^(24g) psi^((2 m1 + 1) j1), j1 >= 1: a copy of the
+// context's tables behind the az planes (gl::mid_limbs on the host, lf_api.hip; built in the
+// block from mid they cost the kernel 23 spilled registers)
+static_assert(3 * MID3_ROWS * 32 == ring::MID3_U64, "limb tables");
+__device__ __forceinline__ void mid3_stage(int2 *mid3, const uint64_t *mid3_g) {
+  for (int q = threadIdx.x; q < ring::MID3_U64; q += blockDim.x) {
+    const uint64_t m = mid3_g[q];
+    mid3[q] = make_int2((int)(uint32_t)m, (int)(uint32_t)(m >> 32));
+  }
 }
 template <bool NT>
 __global__ void __launch_bounds__(512, 1) k_decompose_fused(size_t N, int L, int lb,
-                                                           int K, FusedSides sd, const uint64_t *mid_fg,
-                                                           const uint64_t *az_g, uint4 *frag, int nch,
+                                                           int K, FusedSides sd, const uint64_t *az_g,
+                                                           uint4 *frag, int nch,
                                                            uint64_t *sink) {
   __shared__ uint64_t lds_all[FD_S_U64];
-  __shared__ uint64_t mid2[n32::MID_U64];
+  __shared__ int2 mid3[3 * MID3_ROWS * 32];  // the middle factors' limb pairs, 23.25 KiB (mid3_stage)
   __shared__ uint64_t az_l[1024];  // the 8 KiB of D8 byte planes of zeta^((2 m1 + 1) j2)
   __shared__ uint32_t vote[2][FD_WAVES];  // per wave: its plane is nonzero in the current unit
-  mid2_stage(mid2, mid_fg);
+  mid3_stage(mid3, az_g + 1024);
   for (int q = threadIdx.x; q < 1024; q += blockDim.x) az_l[q] = az_g[q];
   __syncthreads();
   const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
   const int r = lane & 31, h = lane >> 5, hw = 2 * wib + h;  // hw: this half's group within the block
   uint64_t *S = lds_all;
+  const int s_wr = fd_s_index(r, hw);  // this lane's staging column in slot r
   const size_t W = N / L, nblk = (W + 15) / 16;
   const uint64_t b_pow = gl::mul_pow2(1, lb);  // B = 2^lb
   const int8_t *azl = reinterpret_cast<const int8_t *>(az_l);
@@ -715,10 +726,11 @@ __global__ void __launch_bounds__(512, 1) k_decompose_fused(size_t N, int L, int
         const bool live = __ballot((nz & 0x10001u) != 0) != 0;
         if (live) {
           uint64_t y0[16], y1[16];
-          mx_stage1_t(azl, wn, kb, y0, r, h);
-          __builtin_amdgcn_sched_barrier(0);  // one element's products and epilogue at a time (registers)
-          mx_stage1_t(azl, wn + 8, kb, y1, r, h);
-          mid2_apply(mid2, y0, y1, r, h);
+          int32_t G0[3][16], G1[3][16];
+          mx_stage1_t(azl, wn, kb, G0, r, h);
+          __builtin_amdgcn_sched_barrier(0);  // one element's products and sums at a time (registers)
+          mx_stage1_t(azl, wn + 8, kb, G1, r, h);
+          mid3_apply(mid3, G0, G1, y0, y1, r, h);
           n32::halves_to_elements(y0, y1, v);  // lane m1 = r of element h: its 32 j1
         }
         {  // words for the next limb, in flight through the second stage (at l = 0 a
@@ -768,16 +780,19 @@ __global__ void __launch_bounds__(512, 1) k_decompose_fused(size_t N, int L, int
           }
           if (!any) continue;  // block-uniform: no further barrier for this unit
 #pragma unroll
-          for (int i = 0; i < 32; i++) S[(r + 32 * n32::brv5(i)) * FD_SROW + hw] = fenc(v[i]);
+          for (int i = 0; i < 32; i++) S[s_wr + 32 * FD_SROW * n32::brv5(i)] = fenc(v[i]);  // slots r + 32 brv5(i): r's swizzle
           __syncthreads();
           const int c = (int)(u >> 1), uh = (int)(u & 1);
 #pragma unroll
           for (int rep = 0; rep < 2; rep++) {
             const int s = threadIdx.x + 512 * rep;
-            const uint64_t *src = S + s * FD_SROW;
+            // column j of slot s: byte offset 8 fd_s_index(s, j) = b8 ^ 8 j. One xor per read, kept
+            // in the loop: hoisted, the 32 addresses are loop-invariant registers that spill
+            uint32_t b8 = 8u * fd_s_index(s, 0);
+            asm volatile("" : "+v"(b8));
             uint64_t x[16];
 #pragma unroll
-            for (int j = 0; j < 16; j++) x[j] = src[j];
+            for (int j = 0; j < 16; j++) x[j] = *reinterpret_cast<const uint64_t *>(reinterpret_cast<const char *>(S) + (b8 ^ (8u * j)));
             uint4 pu[8];
             d8_transpose16(x, pu);
             uint4 *out = frag + fv_index(s, nch, c, row, uh);
@@ -838,10 +853,10 @@ hipError_t decompose_fused(const FusedSides &sd, size_t N, int lb, int L, int K,
   const size_t out_bytes = sd.nside * (size_t)K * N * D * 8 * 3;
   if (!fwd.az) return hipErrorInvalidValue;
   if (dec_streaming(out_bytes, false))
-    hipLaunchKernelGGL(k_decompose_fused<true>, dim3(grid), dim3(512), 0, st, N, L, lb, K, sd, fwd.mid, fwd.az, frag,
+    hipLaunchKernelGGL(k_decompose_fused<true>, dim3(grid), dim3(512), 0, st, N, L, lb, K, sd, fwd.az, frag,
                        nch, sink);
   else
-    hipLaunchKernelGGL(k_decompose_fused<false>, dim3(grid), dim3(512), 0, st, N, L, lb, K, sd, fwd.mid, fwd.az, frag,
+    hipLaunchKernelGGL(k_decompose_fused<false>, dim3(grid), dim3(512), 0, st, N, L, lb, K, sd, fwd.az, frag,
                        nch, sink);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;

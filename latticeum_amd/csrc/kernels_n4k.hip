@@ -374,7 +374,10 @@ __device__ __forceinline__ void mx_stage1_q(const int8_t *zl, const uint32_t *w4
   quarter(4, q1);
 #pragma unroll
   for (int i = 0; i < 16; i++) {
-    // Y = Q0 + Q1 2^32 (|Q| < 2^39) folded as in kernels_n32.hip mx_stage1
+    // Y = Q0 + Q1 2^32 (|Q| < 2^39) == A + (Q1l + Q1h) 2^32 with Q1 = Q1h 2^32 + Q1l, A = Q0 - Q1h
+    // (2^64 == 2^32 - 1); = A.lo + T 2^32, = U + th 2^64 == U + th EPS with U = T.lo:A.lo and
+    // th = T >> 32 in {-1, 0, 1} (no wrap). The d = 1024 kernel multiplies the middle factors
+    // into grouped sums instead (gl::mul_mid3); these sums reach 2^14, past its bound.
     const int64_t q1h = q1[i] >> 32;
     const int64_t A = q0[i] - q1h;
     const int64_t T = (A >> 32) + (int64_t)(uint32_t)q1[i] + q1h;

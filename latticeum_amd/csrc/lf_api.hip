@@ -30,7 +30,8 @@ int get_tables(lf_ctx *c, int d, Tables *&out) {
     // d = 1024: then the D8 byte planes of zeta^((2 m1 + 1) j2) for the matrix-core stage 1 (1024 u64);
     // d = 4096: the quarters' stage-1 planes Z''_m0 (4 x 4096 u64) and middle factors (4 x 1024)
     const size_t az_off = 4 * (size_t)d + extra;
-    std::vector<uint64_t> h(az_off + (d == 1024 ? 1024 : d == 4096 ? 4 * 4096 + 4 * 1024 : 0));
+    // d = 1024: after the planes, the forward middle factors' limb tables (ring::MID3_U64)
+    std::vector<uint64_t> h(az_off + (d == 1024 ? 1024 + ring::MID3_U64 : d == 4096 ? 4 * 4096 + 4 * 1024 : 0));
     const uint64_t psi = gl::pow(7, (gl::P - 1) / (2 * (uint64_t)d));
     const uint64_t psi_inv = gl::inv(psi), w = gl::mul(psi, psi), w_inv = gl::mul(psi_inv, psi_inv);
     const uint64_t dinv = gl::inv((uint64_t)d);
@@ -72,6 +73,17 @@ int get_tables(lf_ctx *c, int d, Tables *&out) {
             const uint64_t dd = (tt + 0x8080808080808080ull) ^ 0x8080808080808080ull;
             for (int b = 0; b < 8; b++) az[(b * 32 + m1) * 32 + j2] = (int8_t)(uint8_t)(dd >> (8 * b));
           }
+        // mid3[g][j1 - 1][m1] = the signed 32-bit limbs (lo | hi << 32) of 2^(24g) p1^((2 m1 + 1) j1), j1 >= 1
+        // (gl::mid_limbs; row j1 = 0 is the constant 2^(24g)): the middle factors as k_decompose_fused
+        // multiplies them into the grouped byte sums of its matrix-core stage 1
+        uint64_t *m3 = h.data() + az_off + 1024;
+        for (int g = 0; g < 3; g++)
+          for (int j1 = 1; j1 < 32; j1++)
+            for (int m1 = 0; m1 < 32; m1++) {
+              int32_t lo, hi;
+              gl::mid_limbs(h[4 * d + j1 * 32 + brv5(m1)], g, lo, hi);
+              m3[(g * 31 + j1 - 1) * 32 + m1] = (uint64_t)(uint32_t)lo | ((uint64_t)(uint32_t)hi << 32);
+            }
       }
       if (d == 4096) {
         // kernels_n4k.hip relies on psi^1024 = 2^120 (the radix-4 butterflies are shifts)

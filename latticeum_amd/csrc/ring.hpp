@@ -211,6 +211,7 @@ __device__ __forceinline__ void fq3acc_final(const Fq3Acc &s, uint64_t *c) {
 }
 
 // ---------------------------------------------------------------- negacyclic
+constexpr int MID3_U64 = 3 * 31 * 32;  // the limb tables behind NegaTables::az
 struct NegaTables {
   const uint64_t *twist;      // fwd: psi^j ; inv: d^-1 psi^-j
   const uint64_t *roots;      // fwd: omega^e ; inv: omega^-e   (omega = psi^2), e < d
@@ -218,7 +219,8 @@ struct NegaTables {
                               // (d = 4096: those of its 1024-point sub-transforms, kernels_n4k.hip)
   const uint64_t *tw4 = nullptr;   // d = 4096: radix-4 twists [m0][a] (fwd psi^((2m0-3)a), inv 4^-1 psi^-((2m0-3)a))
   const uint64_t *ztab = nullptr;  // d = 4096 fwd: butterflies of four balanced bits [m0][nibble | signs << 4]
-  const uint64_t *az = nullptr;    // d = 1024 fwd: D8 byte planes of zeta^((2 m1 + 1) j2), int8 [8][32][32]
+  const uint64_t *az = nullptr;    // d = 1024 fwd: D8 byte planes of zeta^((2 m1 + 1) j2), int8 [8][32][32], and after
+                                   // them (az + 1024) mid's limb tables [3][31][32] (MID3_U64; lf_api.hip)
   // d = 4096 fwd, stage 1 of each quarter m0 on the matrix cores (kernels_n4k.hip k_decompose_n4k_mx):
   const uint64_t *zq = nullptr;    // D8 byte planes of Z''_m0[m1][32 b + j2], int8 [4][8][32][128]
   const uint64_t *midq = nullptr;  // middle factors with the j1 twist, [4][j1 32][brv5(m1) 32]

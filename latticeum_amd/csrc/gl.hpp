@@ -100,6 +100,41 @@ LF_HD uint64_t mul_mid3(const int32_t G[3], const int32_t lo[3], const int32_t h
   return from_x_y32(X, H);
 }
 
+// The same product with both sums offset by C = 2^61, so that neither can be negative and the
+// fold needs no sign handling: X' = C + X, H' = C + H (C is the addend of each chain's first
+// multiply-add), and with |X|, |H| < 2^60.02 both lie in (0, 2^62). H' = hh 2^32 + hl, hh < 2^30:
+// X' + 2^32 H' == t + hl 2^32 with t = X' + hh (2^32 - 1) < 2^63 (one v_mad_u64_u32, no carry).
+// t2 = t + hl 2^32 with carry c1; after a carry t2 < 2^63, so u = t2 + EPS has not wrapped and
+// is t2 + 2^64 - p < p; without one t2 >= p exactly when u carries (c3): add()'s tail.
+// Returns the canonical Y m + MID3_OFF, MID3_OFF = (C + 2^32 C) mod p = 2^62 - 2^29: the caller
+// owes the subtraction. A transform of 32 such values carries 32 MID3_OFF in its slot 0 and
+// nothing elsewhere (sum_j w^(m j) = 32 [m = 0]): MID3_OFF32 = 32 MID3_OFF mod p = 2^34 - 8.
+constexpr uint64_t MID3_C = 1ull << 61;
+constexpr uint64_t MID3_OFF = 0x3fffffffe0000000ull;
+constexpr uint64_t MID3_OFF32 = 0x3fffffff8ull;
+LF_HD uint64_t from_x_y32_off(uint64_t X, uint64_t H) {  // 0 < X, H < 2^62
+  const uint64_t t = X + (uint64_t)(uint32_t)(H >> 32) * (uint64_t)(uint32_t)EPS;
+  // hl 2^32 has no low word: t2's is t's, and the carry is the high words' own
+  unsigned int c1;
+  const uint32_t th = __builtin_addc((uint32_t)(t >> 32), (uint32_t)H, 0u, &c1);
+  const uint64_t t2 = ((uint64_t)th << 32) | (uint32_t)t;
+  uint64_t u;
+  const bool c3 = addc64(t2, EPS, u);
+  return (c1 | c3) ? u : t2;
+}
+LF_HD uint64_t mul_mid3_off(const int32_t G[3], const int32_t lo[3], const int32_t hi[3]) {
+  int64_t c = (int64_t)MID3_C;
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm("" : "+s"(c));  // opaque: stays the multiply-add's addend (known, it becomes an add to the high word)
+#endif
+  int64_t X = c + (int64_t)G[0] * lo[0], H = c + (int64_t)G[0] * hi[0];
+  X += (int64_t)G[1] * lo[1];
+  H += (int64_t)G[1] * hi[1];
+  X += (int64_t)G[2] * lo[2];
+  H += (int64_t)G[2] * hi[2];
+  return from_x_y32_off((uint64_t)X, (uint64_t)H);
+}
+
 // 64x64 -> 128 from four 32x32 -> 64 multiply-adds (v_mad_u64_u32 each; no
 // intermediate sum overflows: (2^32-1)^2 + 2 (2^32-1) = 2^64 - 1)
 LF_HD void mul_wide(uint64_t a, uint64_t b, uint64_t &lo, uint64_t &hi) {

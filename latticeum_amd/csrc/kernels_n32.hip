@@ -628,9 +628,12 @@ __device__ __forceinline__ void mx_stage1_t(const int8_t *azl, const uint32_t *w
 }
 // y_e = Y_e psi^((2 m1 + 1) j1), m1 = r, for both elements from their grouped sums,
 // with one read of the row's three limb pairs for both (per element: the same
-// 2 spilled registers, 6 more VALU and 26 more LDS reads per body): gl::mul_mid3's
-// six signed 32 x 32 multiply-adds and one fold per value. Row j1 = 0 (register 0
-// of the lower half) is the constants 2^(24g) and is not stored.
+// 2 spilled registers, 6 more VALU and 26 more LDS reads per body): gl::mul_mid3_off's
+// six signed 32 x 32 multiply-adds and one unsigned fold per value. Row j1 = 0 (register 0
+// of the lower half) is the constants 2^(24g) and is not stored. Every value, row 0's too,
+// comes out as y + gl::MID3_OFF; stage 2 is linear, so its 32 offsets meet in slot 0 alone
+// and the caller takes gl::MID3_OFF32 off v[0] after cyc_dif32 (once per lane, against a
+// signed fold per value).
 __device__ __forceinline__ void mid3_apply(const int2 *mid3, const int32_t (*G0)[16], const int32_t (*G1)[16], uint64_t *y0,
                                            uint64_t *y1, int r, int h) {
 #pragma unroll
@@ -645,8 +648,8 @@ __device__ __forceinline__ void mid3_apply(const int2 *mid3, const int32_t (*G0)
       if (i == 0 && h == 0) lo[g] = g == 1 ? 1 << 24 : g == 0, hi[g] = g == 2 ? 1 << 16 : 0;
     }
     const int32_t g0[3] = {G0[0][i], G0[1][i], G0[2][i]}, g1[3] = {G1[0][i], G1[1][i], G1[2][i]};
-    y0[i] = gl::mul_mid3(g0, lo, hi);
-    y1[i] = gl::mul_mid3(g1, lo, hi);
+    y0[i] = gl::mul_mid3_off(g0, lo, hi);
+    y1[i] = gl::mul_mid3_off(g1, lo, hi);
   }
 }
 // mid3[g][j1 - 1][m1] = the limbs (lo, hi) of 2^(24g) psi^((2 m1 + 1) j1), j1 >= 1: a copy of the
@@ -741,6 +744,7 @@ __global__ void __launch_bounds__(512, 1) k_decompose_fused(size_t N, int L, int
         }
         if (live) {
           n32::cyc_dif32<false>(v);
+          v[0] = gl::sub(v[0], gl::MID3_OFF32);  // the middle factors' 32 offsets (mid3_apply), slot m2 = 0
         } else {
 #pragma unroll
           for (int j = 0; j < 32; j++) v[j] = 0;

@@ -374,7 +374,8 @@ typedef struct {
    * element is d / 2 u32, and word j (j < d / 2) of element e sits at e d / 2 + j
    * and holds coefficient j in its low half and coefficient j + d / 2 in its high
    * half. planes beside fk: both are written; with fk NULL f_0 is folded from the
-   * operand rows.
+   * packed words themselves, on the matrix cores (lf_dev_fold_planes's product), and from
+   * the operand rows only for a rho that is not short (lf_ctx_fold_flag).
    * d = 2048 has no packed form (sixteen elements' transform tile, 256 KiB, does
    * not fit a compute unit's LDS): planes, or NULL fk, are refused there as before.
    * lf_fold_step_planes_len gives the length of one side's buffer. */
@@ -390,6 +391,27 @@ size_t lf_fold_step_planes_len(const lf_params *pr, size_t N);
  * f_coeff_k [K][N] (digits mod p) and / or f_k [K][N] = CRT(f_coeff_k); either may be NULL */
 int lf_dev_expand_planes(lf_ctx *ctx, const lf_params *pr, const uint64_t *planes, size_t N, uint64_t *f_coeff_k,
                          uint64_t *f_k);
+/* compute_f_0 (folding.rs:258-268) and Witness::from_f (arith.rs:299-313) from the packed
+ * digit planes of both sides alone: f0_coeff, f0 [N], w_ccs0 [N / L]. planes0 / planes1:
+ * lf_fold_step_bufs.planes of side 0 (the accumulator) and side 1, N elements each; rho: the
+ * 2K challenges in NTT form, rho[s K + k] for plane k of side s. All pointers are device
+ * memory. The product is the exact integer sum_i rho_i * D_i over the digit planes D_i on the
+ * i8 matrix cores; the outputs are the bits of fold()'s.
+ * Rings: d = 16 .. 512 and d = 1024 (X^d + 1), d = 24; b_small = 2, K <= 15. LF_ERR_UNSUPPORTED_RING
+ * otherwise: d = 2048 has no packed form, and at d = 4096 the product has the multiply-add
+ * count of d = 1024's against a fold from the operand rows that is twice as fast (DESIGN.md
+ * section 4), so none is built. LF_ERR_INCORRECT_LENGTH when N is not a multiple of L,
+ * LF_ERR_INVALID_ARG for a NULL pointer.
+ * It reads no state of any earlier step: a context that has never run a step gives the same
+ * bits. Asynchronous on the context's stream.
+ * Defined for a short rho only: every coefficient of every rho_i in [-127, 127] ([-32, 32] at
+ * d = 24), which is all get_rhos produces. There are no rows here to fall back on, so a rho
+ * outside that range raises a device flag of its own (not the decomposition-overflow one):
+ * the next lf_ctx_sync returns LF_ERR_INVALID_ARG with the cause in lf_ctx_last_error and
+ * clears the flag, lf_ctx_fold_flag gives 1, and the outputs are unspecified (nothing is read
+ * or written out of bounds). */
+int lf_dev_fold_planes(lf_ctx *ctx, const lf_params *pr, const uint64_t *planes0, const uint64_t *planes1,
+                       size_t N, const uint64_t *rho, uint64_t *f0_coeff, uint64_t *f0, uint64_t *w_ccs0);
 /* commit(z) followed by the commit+fold arithmetic of fold(), all on device */
 int lf_dev_fold_step(lf_ctx *ctx, const lf_ajtai *aj, const lf_params *pr, size_t W,
                      const lf_fold_step_bufs *b);
@@ -472,13 +494,15 @@ int lf_dev_poseidon2_permute_rounds(lf_ctx *ctx, uint64_t *states, size_t n, int
 int lf_dev_gl_probe(lf_ctx *ctx, int op, const uint64_t *a, const uint64_t *b, int s, int m, uint64_t *out,
                     size_t n);
 /* test aid: whether the context's last fold step (lf_dev_fold_step and its batch, partial /
- * finish and lf_dev_fold_combine forms, lf_fold_hot) judged rho short. The coefficient-form
- * folds (d = 1024 after the fused decomposition: every coefficient of every rho_i in
- * [-127, 127]; d = 24 with b_small = 2: in [-32, 32]) decide it on the device, per step, with
- * no host synchronisation; this call waits for the context's stream and reads that flag:
- * *out = 0 rho was short and f_0 was folded in coefficient form, 1 it was not and the
- * NTT-form fold ran instead, -1 the step took a path that has no such flag. It launches
- * nothing and leaves the decomposition-overflow state to lf_ctx_sync. In a batch every step's
+ * finish and lf_dev_fold_combine forms, lf_fold_hot) or lf_dev_fold_planes judged rho short.
+ * The coefficient-form folds (d = 1024 after the fused decomposition, and d = 16 .. 512 on a
+ * step with packed planes or scratch words and no f_k buffers: every coefficient of every
+ * rho_i in [-127, 127]; d = 24 with b_small = 2: in [-32, 32]) decide it on the device, per
+ * step, with no host synchronisation; this call waits for the context's stream and reads that
+ * flag: *out = 0 rho was short and f_0 was folded in coefficient form, 1 it was not and the
+ * NTT-form fold ran instead (after lf_dev_fold_planes: nothing did), -1 the step took a path
+ * that has no such flag (at d = 16 .. 512: a step with f_k buffers, or one without the fused
+ * decomposition). It launches nothing and leaves the decomposition-overflow state to lf_ctx_sync. In a batch every step's
  * context reports its own step. */
 int lf_ctx_fold_flag(lf_ctx *ctx, int *out);
 /* test aid beside lf_ctx_fold_flag: the level of the Karatsuba split of the Toeplitz

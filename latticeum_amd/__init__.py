@@ -413,6 +413,13 @@ class Context:
                                                  _dptr(f_coeff_k) if f_coeff_k is not None else None,
                                                  _dptr(f_k) if f_k is not None else None))
 
+    def dev_fold_planes(self, params: LfParams, planes0, planes1, N: int, rho, f0_coeff, f0, w_ccs0):
+        """compute_f_0 and Witness::from_f from both sides' packed digit planes (N elements each)
+        and the 2K NTT-form challenges alone (lf_dev_fold_planes): f0_coeff, f0 [N], w_ccs0 [N / L].
+        Asynchronous; a rho that is not short makes the next sync() raise LF_ERR_INVALID_ARG"""
+        self.check(self.lib.lf_dev_fold_planes(self.h, C.byref(params), _dptr(planes0), _dptr(planes1), N,
+                                               _dptr(rho), _dptr(f0_coeff), _dptr(f0), _dptr(w_ccs0)))
+
     def dev_get_fhat(self, d, f_coeff, N, nv, out):
         """Witness::get_fhat on the device: out [tau][2^nv][d] from f_coeff [N][d]"""
         self.check(self.lib.lf_dev_get_fhat(self.h, d, _dptr(f_coeff), N, nv, _dptr(out)))

@@ -2,6 +2,8 @@
 // (lf_api.hip, api_step.hip, api_sumcheck.hip, api_ccs.hip, api_memtree.hip, fold_prove.hip): the
 // context and the other handles, the error / scratch / host-buffer helpers, and
 // the two transcript steps every Fiat-Shamir loop is made of.
+// The device error word (lf_ctx::d_err): bit 0 = a decomposition overflowed (digits.hpp
+// raise), bit 1 = lf_dev_fold_planes was given a rho that is not short (LF_DERR_RHO).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>  // types only: the RCCL entry points are resolved at run time (lf_api.hip rccl())
@@ -15,6 +17,8 @@
 #include "gl.hpp"
 #include "kernels.hpp"
 #include "launch.hpp"
+
+constexpr int LF_DERR_RHO = 2;
 
 struct Tables {
   uint64_t *mem = nullptr;  // 4*d u64: fwd twist | fwd roots | inv twist | inv roots
@@ -36,15 +40,16 @@ enum class FoldPath {
   Rows,           // NTT-form fold from the operand rows (a step without f_k buffers)
   Coeff1024,      // d = 1024: coefficient-form fold from the packed digits
   Coeff1024Rows,  // the same on packed planes: a rho that is not short folds from the operand rows in that launch
+  CoeffPow2,      // d = 16 .. 512 without f_k: coefficient-form fold from the packed words, the operand rows for such a rho
   Masks24,        // Phi_72: coefficient-form fold from the digit masks, f_k rows for a rho that is not short
   Masks24Packed,  // the same on packed planes: such a rho folds from the masks in Z_p
 };
 struct StepState {
   FoldPath path = FoldPath::Ntt;
   size_t N = 0;                                // the witness length the state was made for
-  uint32_t *smg_side[2] = {nullptr, nullptr};  // Coeff1024*: both sides' packed words (the caller's planes, or smg)
+  uint32_t *smg_side[2] = {nullptr, nullptr};  // Coeff1024*, CoeffPow2: both sides' packed words (the caller's planes, or smg)
   const uint2 *masks24[2] = {nullptr, nullptr};  // Masks24*: both sides' digit masks (fkeys or the caller's planes)
-  lfk::FoldRows fold_rows{};    // Rows, Coeff1024Rows: where the 2K planes sit in the operand rows
+  lfk::FoldRows fold_rows{};    // Rows, Coeff1024Rows, CoeffPow2: where the 2K planes sit in the operand rows
   lfk::DeadUnits dead_units{};  // the fused decomposition's flags (what the readers of c->frag honour)
 };
 

@@ -4,6 +4,8 @@
 #include <algorithm>
 
 #include "api_internal.hpp"
+#include "foldpow2.hpp"
+#include "wsrc.hpp"
 
 namespace {
 
@@ -70,7 +72,8 @@ StepPlan step_plan(const lf_ajtai *aj, const lf_params *pr, int lbs, const Table
     // d = 16 .. 512 (decompose_pow2.hip): only for a caller who opted in, with planes
     // or without f_k buffers; with f_k and no planes the step stays Plain
     p.dec = Decomp::FusedPow2;
-    p.path = no_fk ? FoldPath::Rows : FoldPath::Ntt;
+    // f_0 from the packed words: faster than from the operand rows at every degree measured
+    p.path = no_fk ? FoldPath::CoeffPow2 : FoldPath::Ntt;
   }
   return p;
 }
@@ -124,7 +127,9 @@ int decompose_n4k_sides(lf_ctx *c, const Tables *t, lfk::FusedSides &sd, size_t 
                         uint4 *frag = nullptr, int nch = 0) {
   const bool own = !(frag && sd.smg[0]);
   // the smg scratch a d = 1024 step's coefficient fold would read may be overwritten here
-  if (c->step.path == FoldPath::Coeff1024 || c->step.path == FoldPath::Coeff1024Rows) c->step = {};
+  if (c->step.path == FoldPath::Coeff1024 || c->step.path == FoldPath::Coeff1024Rows ||
+      c->step.path == FoldPath::CoeffPow2)
+    c->step = {};
   if (own) LF_TRY(grow(c, c->smg, c->smg_elems, (size_t)sd.nside * N * (frag ? lfk::sm8_words(K) : 2 * lfk::SM4_WORDS)));
   LF_HIP(c, lfk::decompose_n4k(sd, N, lb, L, K, own ? reinterpret_cast<uint64_t *>(c->smg) : nullptr, t->fwd, c->d_err,
                                c->sink, c->ncu, c->cur, frag, nch));
@@ -262,7 +267,8 @@ int fold_commit(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, int lb, int 
     const size_t words = N * lfk::smp2_words(d);
     if (!b->planes[0]) LF_TRY(grow(c, c->smg, c->smg_elems, 2 * words));
     for (int s = 0; s < 2; s++)
-      sd.smg[s] = b->planes[0] ? reinterpret_cast<uint32_t *>(b->planes[s]) : c->smg + (size_t)s * words;
+      st.smg_side[s] = sd.smg[s] =
+          b->planes[0] ? reinterpret_cast<uint32_t *>(b->planes[s]) : c->smg + (size_t)s * words;
     PhaseTimer pt(c, LF_PHASE_DECOMPOSE);  // both sides in one launch
     LF_HIP(c, lfk::decompose_pow2(sd, N, d, lb, L, K, t->fwd, c->frag, aj->geom.nch, c->d_err, c->cur));
   } else if (fused) {
@@ -340,6 +346,23 @@ lfk::OutPtrs fold_dst(const lf_params *pr, const lf_fold_step_bufs *b, size_t kd
   for (int s = 0; s < 2; s++)
     for (int k = 1; k < pr->K; k++) dst.p[extra + s * (pr->K - 1) + k - 1] = b->y[s] + (size_t)k * kd;
   return dst;
+}
+
+// the coefficient-form product at d = 16 .. 512: the rho tables and the not-short flag
+// (both in faux; lf_ctx_fold_flag reads the flag), then f0_coeff unless the flag is up
+int fold_pow2_coeff(lf_ctx *c, const lf_params *pr, const Tables *t, const uint32_t *sm0, const uint32_t *sm1,
+                    size_t N, const uint64_t *rho, uint64_t *f0_coeff, int *&bad) {
+  const int d = pr->d, K = pr->K, nw = 2 * K;
+  const size_t tab_u64 = ((size_t)nw * lfk::fp2_tab_bytes(d) + 7) / 8;
+  LF_TRY(grow(c, c->faux, c->faux_elems, tab_u64 + 1));
+  uint8_t *tab = reinterpret_cast<uint8_t *>(c->faux);
+  bad = reinterpret_cast<int *>(c->faux + tab_u64);
+  c->fold_flag_at = (long)tab_u64;
+  LF_HIP(c, lfk::fold_pow2_rho_tables(rho, nw, d, tab, bad, t->inv, c->d_sync, c->cur));
+  const int ks_n = lfk::fold_pow2_splits(N, d, K, c->ncu);
+  if (ks_n > 1) LF_TRY(grow(c, c->fpart, c->fpart_elems, (size_t)ks_n * N * d));
+  LF_HIP(c, lfk::fold_coeff_pow2(sm0, sm1, tab, bad, N, d, K, f0_coeff, c->ncu, c->cur, ks_n > 1 ? c->fpart : nullptr));
+  return LF_OK;
 }
 
 int fold_finish(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, int lb, int lbs, size_t W,
@@ -424,6 +447,23 @@ int fold_finish(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, int lb, int 
           LF_HIP(c, lfk::fold(b->rho, fk_rows(), nw, N, d, b->f0, c->cur, bad));
       }
       PhaseTimer pt(c, LF_PHASE_FROM_F);
+      LF_HIP(c, lfk::from_f(b->f0, N, d, lb, L, b->f0_coeff, b->w_ccs0, t->inv, c->cur, bad));
+      return LF_OK;
+    }
+    // d = 16 .. 512 after the fused decomposition, no f_k: f_0 in coefficient form on the
+    // matrix cores from the packed words (fold_coeff_pow2.hip), then f_0 and w_ccs by one
+    // forward transform per element. If a rho is not short the device flag `bad` turns
+    // those launches off and the fold from the operand rows and from_f on.
+    case FoldPath::CoeffPow2: {
+      int *bad;
+      {
+        PhaseTimer pt(c, LF_PHASE_FOLD);
+        LF_TRY(fold_pow2_coeff(c, pr, t, st.smg_side[0], st.smg_side[1], N, b->rho, b->f0_coeff, bad));
+        LF_HIP(c, lfk::fold_frag(c->frag, aj->geom, st.fold_rows, b->rho, d, N, b->f0, c->cur, bad));
+      }
+      PhaseTimer pt(c, LF_PHASE_FROM_F);
+      LF_HIP(c, lfk::from_fcoeff(b->f0_coeff, lfk::WSRC_U64, N, d, lb, L, nullptr, b->f0, b->w_ccs0, t->fwd, nullptr,
+                                 c->cur, bad));
       LF_HIP(c, lfk::from_f(b->f0, N, d, lb, L, b->f0_coeff, b->w_ccs0, t->inv, c->cur, bad));
       return LF_OK;
     }
@@ -631,6 +671,63 @@ int lf_dev_expand_planes(lf_ctx *c, const lf_params *pr, const uint64_t *planes,
     if (fck) LF_HIP(c, hipMemcpyAsync(fk, fck, (size_t)K * N * d * 8, hipMemcpyDeviceToDevice, c->cur));
     LF_TRY(lf_dev_crt(c, fk, (size_t)K * N, d));
   }
+  return LF_OK;
+}
+
+int lf_dev_fold_planes(lf_ctx *c, const lf_params *pr, const uint64_t *planes0, const uint64_t *planes1, size_t N,
+                       const uint64_t *rho, uint64_t *f0_coeff, uint64_t *f0, uint64_t *w_ccs0) {
+  if (!c) return LF_ERR_INVALID_ARG;
+  DevGuard g(c);
+  int lb, lbs;
+  LF_TRY(check_params(c, pr, lb, lbs));
+  const int d = pr->d, K = pr->K, L = pr->L, nw = 2 * K;
+  if (!planes0 || !planes1 || !rho || !f0_coeff || !f0 || !w_ccs0) return fail(c, LF_ERR_INVALID_ARG, "fold_planes: NULL pointer");
+  if ((d != 24 && d != 1024 && !lfk::smp2_degree(d)) || lbs != 1 || K > 15)
+    return fail(c, LF_ERR_UNSUPPORTED_RING, "fold_planes: d = 24, 16 .. 512 or 1024, b_small = 2, K <= 15");
+  if (N % L) return fail(c, LF_ERR_INCORRECT_LENGTH, "N must be a multiple of L");
+  if (!N) return LF_OK;
+  Tables *t;
+  LF_TRY(get_tables(c, d, t));
+  const size_t W = N / L;
+  c->fold_has_level = false;
+  int *bad;
+  if (d == 24) {
+    const uint2 *m0 = reinterpret_cast<const uint2 *>(planes0), *m1 = reinterpret_cast<const uint2 *>(planes1);
+    LF_TRY(grow(c, c->faux, c->faux_elems, (size_t)nw * 13 + 1));
+    uint32_t *rc = reinterpret_cast<uint32_t *>(c->faux);  // 25 packed words per witness
+    bad = reinterpret_cast<int *>(c->faux + (size_t)nw * 13);
+    c->fold_flag_at = (long)nw * 13;
+    LF_HIP(c, lfk::fold_phi72_rho(rho, nw, rc, bad, c->cur));
+    LF_HIP(c, lfk::fold_phi72_coeff(m0, m1, rc, bad, N, K, L, lb, f0_coeff, f0, w_ccs0, c->cur));
+  } else if (d == 1024) {
+    if (!t->fwd.mid || !t->inv.mid) return fail(c, LF_ERR_UNSUPPORTED_RING, "fold_planes: no d = 1024 register transform");
+    // a pending Phi_72 step's masks may live in fkeys: its fold_combine takes the f_k rows instead
+    if (c->step.path == FoldPath::Masks24) c->step = {};
+    const size_t tab_u64 = (lfk::fold_tab_bytes(nw) + 7) / 8, aux = (size_t)nw * 1024 + tab_u64 + 1;
+    const int kara = lfk::fold_kara_cap();
+    LF_TRY(grow(c, c->fkeys, c->fkeys_elems, 2 * N * (size_t)K * 64 + 2 * N));
+    uint32_t *nz = c->fkeys + 2 * N * (size_t)K * 64;
+    LF_TRY(grow(c, c->faux, c->faux_elems, aux));
+    uint8_t *tab = reinterpret_cast<uint8_t *>(c->faux + (size_t)nw * 1024);
+    bad = reinterpret_cast<int *>(c->faux + aux - 1);
+    c->fold_flag_at = (long)(aux - 1);
+    c->fold_has_level = true;
+    const uint32_t *sm[2] = {reinterpret_cast<const uint32_t *>(planes0), reinterpret_cast<const uint32_t *>(planes1)};
+    for (int s = 0; s < 2; s++)
+      LF_HIP(c, lfk::fold_keys(sm[s], N, K, c->fkeys + (size_t)s * N * K * 64, c->cur, nz + (size_t)s * N));
+    LF_HIP(c, lfk::fold_rho_tables(rho, nw, c->faux, tab, bad, t->inv, c->d_sync, c->cur, kara));
+    const int ks_n = lfk::fold_coeff_splits(N, K, c->ncu);
+    if (ks_n > 1) LF_TRY(grow(c, c->fpart, c->fpart_elems, (size_t)ks_n * N * 1024));
+    LF_HIP(c, lfk::fold_coeff(c->fkeys, tab, bad, N, K, f0_coeff, c->ncu, c->cur, ks_n > 1 ? c->fpart : nullptr, nullptr,
+                              L, nz, kara));
+    LF_HIP(c, lfk::from_fcoeff_n32(f0_coeff, W, lb, L, f0, w_ccs0, t->fwd, bad, c->cur));
+  } else {
+    LF_TRY(fold_pow2_coeff(c, pr, t, reinterpret_cast<const uint32_t *>(planes0),
+                           reinterpret_cast<const uint32_t *>(planes1), N, rho, f0_coeff, bad));
+    LF_HIP(c, lfk::from_fcoeff(f0_coeff, lfk::WSRC_U64, N, d, lb, L, nullptr, f0, w_ccs0, t->fwd, nullptr, c->cur, bad));
+  }
+  // a rho that is not short is the caller's error here: lf_ctx_sync reports it
+  LF_HIP(c, lfk::flag_to_err(bad, c->d_err, LF_DERR_RHO, c->cur));
   return LF_OK;
 }
 

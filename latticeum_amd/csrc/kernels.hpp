@@ -55,8 +55,8 @@ hipError_t mont(uint64_t *x, size_t n, bool to, hipStream_t st);
 hipError_t from_w_ccs(const uint64_t *w_ccs, size_t W, int d, int lb, int L, uint64_t *f_coeff,
                       uint64_t *f, const ring::NegaTables &fwd, const ring::NegaTables &inv, int *err,
                       hipStream_t st, uint32_t *smg = nullptr);
-// run_if (X^1024 + 1 and Phi_72): when given, the kernels do nothing unless *run_if != 0
-// (the fallbacks of the coefficient-form fold, fold_coeff.hip)
+// run_if (every ring but X^4096 + 1): when given, the kernels do nothing unless *run_if != 0
+// (the fallbacks of the coefficient-form folds, fold_coeff.hip and fold_coeff_pow2.hip)
 hipError_t from_f(const uint64_t *f, size_t N, int d, int lb, int L, uint64_t *f_coeff,
                   uint64_t *w_ccs, const ring::NegaTables &inv, hipStream_t st, const int *run_if = nullptr);
 // d = 24 with frag: planes 1..K-1 also written as i8-MFMA operand rows row0.. (Lp = L order, nch chunks)
@@ -273,6 +273,22 @@ hipError_t from_fcoeff_n32(uint64_t *f_coeff, size_t W, int lb, int L, uint64_t 
                            const ring::NegaTables &fwd, const int *gate, hipStream_t st,
                            const ring::NegaTables *inv = nullptr);
 
+// ---------------------------------------------------------------- coefficient-form fold, d = 16 .. 512 (fold_coeff_pow2.hip)
+// f_0 in coefficient form on the i8 matrix cores from both sides' packed words (smp2_*),
+// b_small = 2, K <= 15: rho (nw = 2K NTT elements) -> tab [nw][fp2_tab_bytes(d)] bytes
+// (foldpow2.hpp; 16-byte aligned), *bad = 1 if a coefficient is outside [-127, 127], else 0;
+// sync: two ints, zero before the first launch, left zero by every launch
+hipError_t fold_pow2_rho_tables(const uint64_t *rho, int nw, int d, uint8_t *tab, int *bad,
+                                const ring::NegaTables &inv, int *sync, hipStream_t st);
+// witness splits for N elements (1: none); part: fold_pow2_splits() N d int32 of scratch
+// for the splits' partial sums (or null: no split). Writes f0c = the canonical
+// coefficients of sum_i rho_i f_i unless *bad, when it writes nothing
+int fold_pow2_splits(size_t N, int d, int K, int ncu);
+hipError_t fold_coeff_pow2(const uint32_t *sm0, const uint32_t *sm1, const uint8_t *tab, const int *bad, size_t N,
+                           int d, int K, uint64_t *f0c, int ncu, hipStream_t st, int32_t *part = nullptr);
+// *err |= bit when *flag != 0, on the stream
+hipError_t flag_to_err(const int *flag, int *err, int bit, hipStream_t st);
+
 // ---------------------------------------------------------------- Phi_72 decomposition (decompose_phi72.hip)
 // d = 24: both sides of a fold step in one launch (blockIdx.z = side); frag as decompose_witness
 // *masks_written: whether the launch filled sd.masks (the wave-local kernel does);
@@ -316,9 +332,12 @@ hipError_t from_w_ccs_n4k(const uint64_t *w_ccs, size_t W, int lb, int L, uint64
 // f = CRT(f_coeff) over N elements, w_ccs = recompose(f) over N / L, at every ring. src holds
 // the N d coefficients as the words of source `kind` (wsrc.hpp WitnessSrc: canonical u64, or a
 // packed payload's i16 / i32 / checked u64); fc_out (may be null) gets them in canonical form
-// from the same launch. err: raised by a checked u64 word >= p.
+// from the same launch. err: raised by a checked u64 word >= p. skip_if (d = 16 .. 512 and
+// 2048 only): when given, the kernel does nothing if *skip_if != 0 (the coefficient-form
+// fold at d = 16 .. 512 wrote no f_coeff: its fallback runs instead)
 hipError_t from_fcoeff(const void *src, int kind, size_t N, int d, int lb, int L, uint64_t *fc_out, uint64_t *f,
-                       uint64_t *w_ccs, const ring::NegaTables &fwd, int *err, hipStream_t st);
+                       uint64_t *w_ccs, const ring::NegaTables &fwd, int *err, hipStream_t st,
+                       const int *skip_if = nullptr);
 // its d = 1024 (a source other than plain f_coeff) and d = 4096 forms, on the register-resident 32 x 32 NTT
 hipError_t from_fcoeff_src_n32(const void *src, int kind, size_t W, int lb, int L, uint64_t *fc_out, uint64_t *f,
                                uint64_t *w_ccs, const ring::NegaTables &fwd, int *err, hipStream_t st);

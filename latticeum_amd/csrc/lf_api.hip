@@ -459,7 +459,9 @@ int lf_ctx_sync(lf_ctx *c) {
   LF_HIP(c, hipMemcpy(&e, c->d_err, sizeof(int), hipMemcpyDeviceToHost));
   if (e) {
     LF_HIP(c, hipMemset(c->d_err, 0, sizeof(int)));
-    return fail(c, LF_ERR_DECOMPOSITION_OVERFLOW, "a coefficient needed more digits than padding_size");
+    if (e & ~LF_DERR_RHO)
+      return fail(c, LF_ERR_DECOMPOSITION_OVERFLOW, "a coefficient needed more digits than padding_size");
+    return fail(c, LF_ERR_INVALID_ARG, "lf_dev_fold_planes: a coefficient of rho is outside the short range");
   }
   return LF_OK;
 }

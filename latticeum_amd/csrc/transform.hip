@@ -250,9 +250,10 @@ __global__ void __launch_bounds__(256) k_from_f_phi72(const uint64_t *f, size_t 
 template <int D>
 __global__ void __launch_bounds__(NT<D>::T) k_from_f_nega(const uint64_t *f, size_t W, int lb, int L,
                                                          uint64_t *f_coeff, uint64_t *w_ccs,
-                                                         ring::NegaTables inv) {
+                                                         ring::NegaTables inv, const int *run_if) {
   constexpr int T = NT<D>::T, PER = D / T;
   __shared__ uint64_t buf[2][D];
+  if (run_if && !*run_if) return;  // uniform: the coefficient-form fold produced f_coeff and w_ccs
   const int tid = threadIdx.x;
   for (size_t j = blockIdx.x; j < W; j += gridDim.x) {
     uint64_t acc[PER];
@@ -290,12 +291,11 @@ hipError_t from_f(const uint64_t *f, size_t N, int d, int lb, int L, uint64_t *f
                        W, lb, L, f_coeff, w_ccs, run_if);
     return hipGetLastError();
   }
-  if (run_if) return hipErrorInvalidValue;
-  if (d == 4096 && inv.tw4) return from_f_n4k(f, W, lb, L, f_coeff, w_ccs, inv, st);
+  if (d == 4096 && inv.tw4) return run_if ? hipErrorInvalidValue : from_f_n4k(f, W, lb, L, f_coeff, w_ccs, inv, st);
   return nega_degree(d, [&](auto dd) {
     constexpr int D = decltype(dd)::value;
     hipLaunchKernelGGL((k_from_f_nega<D>), dim3(grid_cap(W)), dim3(NT<D>::T), 0, st, f, W, lb, L, f_coeff, w_ccs,
-                       inv);
+                       inv, run_if);
     return hipGetLastError();
   });
 }

@@ -27,9 +27,10 @@ using ring::NT;
 template <int D, class S>
 __global__ void __launch_bounds__(NT<D>::T) k_from_fcoeff_nega(const typename S::word *src, size_t W, int lb, int L,
                                                               uint64_t *fc_out, uint64_t *f, uint64_t *w_ccs,
-                                                              ring::NegaTables fwd, int *err) {
+                                                              ring::NegaTables fwd, int *err, const int *skip_if) {
   constexpr int T = NT<D>::T, PER = D / T;
   __shared__ uint64_t buf[2][D];
+  if (skip_if && *skip_if) return;  // uniform: the coefficient-form fold wrote no f_coeff (its fallback runs)
   const int tid = threadIdx.x;
   bool bad = false;
   for (size_t j = blockIdx.x; j < W; j += gridDim.x) {
@@ -314,10 +315,11 @@ hipError_t from_fcoeff_n4k(const void *src, int kind, size_t W, int lb, int L, u
 using WitnessNegaDegrees = std::integer_sequence<int, 16, 32, 64, 128, 256, 512, 2048>;
 
 hipError_t from_fcoeff(const void *src, int kind, size_t N, int d, int lb, int L, uint64_t *fc_out, uint64_t *f,
-                       uint64_t *w_ccs, const ring::NegaTables &fwd, int *err, hipStream_t st) {
+                       uint64_t *w_ccs, const ring::NegaTables &fwd, int *err, hipStream_t st, const int *skip_if) {
   if (L < 1) return hipErrorInvalidValue;
   const size_t W = N / L;
   if (W == 0) return hipSuccess;
+  if (skip_if && (d == 1024 || d == 4096 || d == 24)) return hipErrorInvalidValue;  // the LDS-transform kernel's gate
   if (d == 1024) {
     // canonical words and nothing else to write: the coefficient-form fold's launcher, ungated
     if (kind == WSRC_U64 && !fc_out)
@@ -343,7 +345,7 @@ hipError_t from_fcoeff(const void *src, int kind, size_t N, int d, int lb, int L
         return witness_src(kind, [&](auto s) {
           using S = decltype(s);
           hipLaunchKernelGGL((k_from_fcoeff_nega<D, S>), dim3(grid_cap(W)), dim3(NT<D>::T), 0, st,
-                             static_cast<const typename S::word *>(src), W, lb, L, fc_out, f, w_ccs, fwd, err);
+                             static_cast<const typename S::word *>(src), W, lb, L, fc_out, f, w_ccs, fwd, err, skip_if);
           return hipGetLastError();
         });
       },

@@ -24,9 +24,9 @@ PHASE_KERNELS = {
     "decompose": ("k_decompose_fused", "k_decompose_phi72_w", "k_decompose_n4k_mx", "k_decompose_n4k_fused", "k_decompose_n4k",
                   "k_pack_sm", "k_pack_sm24", "k_pack_sm8", "k_pack_sm4", "k_expand_sm"),
     "fold": ("k_fold_coeff", "k_fold_coeff_phi72", "k_fold_nega", "k_fold_frag", "k_fold_coeff_sum", "k_pack_keys",
-             "k_rho_prep", "k_rho_phi72", "k_fold_phi72_masks"),
+             "k_rho_prep", "k_rho_phi72", "k_fold_phi72_masks", "k_fold_coeff_pow2", "k_rho_prep_pow2", "k_fold_pow2_sum"),
     "from_f": ("k_from_fcoeff_n32", "k_from_fcoeff_split", "k_from_f_phi72", "k_from_f_n4k", "k_from_f_n32",
-               "k_from_f_split"),
+               "k_from_f_split", "k_from_fcoeff_nega", "k_from_f_nega"),
     "from_w_ccs": ("k_from_w_ccs_n32", "k_from_w_ccs_digits", "k_from_w_ccs_phi72", "k_from_w_ccs_n4k", "k_xform_n32"),
     "to_frag": ("k_to_frag",),
     "ajtai": ("k_ajtai_mfma_ra",),

@@ -409,9 +409,36 @@ int lf_dev_expand_planes(lf_ctx *ctx, const lf_params *pr, const uint64_t *plane
  * outside that range raises a device flag of its own (not the decomposition-overflow one):
  * the next lf_ctx_sync returns LF_ERR_INVALID_ARG with the cause in lf_ctx_last_error and
  * clears the flag, lf_ctx_fold_flag gives 1, and the outputs are unspecified (nothing is read
- * or written out of bounds). */
+ * or written out of bounds).
+ * The commitments are not part of it: lf_dev_commit_planes makes the y_s[k] (and side 1's cm)
+ * from the same planes, and cm_0 = sum_i rho_i y_i is lf_dev_fold over those 2K rows. */
 int lf_dev_fold_planes(lf_ctx *ctx, const lf_params *pr, const uint64_t *planes0, const uint64_t *planes1,
                        size_t N, const uint64_t *rho, uint64_t *f0_coeff, uint64_t *f0, uint64_t *w_ccs0);
+/* decompose_witness's commitments (commit_witnesses, decomposition.rs:178-201) from the packed
+ * digit planes alone: for each side s < nside (1 or 2) and plane k < K,
+ *   y[s][k] = A · NTT(D_(s,k))                    [K][kappa] ring elements, canonical
+ *   cm[s]   = sum_k b_small^k y[s][k]             kappa   (may be NULL)
+ *   wk[s][k] = sum_l B^l NTT(D_(s,k))[g L + l]    [K][W]  (may be NULL)
+ * planes[s]: lf_fold_step_bufs.planes of N = aj's width elements, decoded exactly as
+ * lf_dev_expand_planes decodes them. cm and wk may be NULL as a whole or per side. All pointers
+ * but the three tables themselves are device memory. Plane 0 is contracted as a row of its own
+ * like the others (y[s][0] is not cm - sum_(k>=1) b^k y[s][k]), both sides go through one pass
+ * over A on the i8 matrix cores, and no [K][N][d] u64 row is allocated or written.
+ * Rings: wherever lf_fold_step_planes_len(pr, N) != 0 (d = 24, 16 .. 512, 1024, 4096; b_small = 2,
+ * K <= 15), else LF_ERR_UNSUPPORTED_RING. A scheme or params for which a step with planes as the
+ * only form is refused (no operand fragments grouped by this L, kappa > 128; at d = 24 also
+ * (L - 1) log2 B >= 62) gets that step's status, LF_ERR_INVALID_ARG. LF_ERR_INCORRECT_LENGTH when N is
+ * not a multiple of L or not aj's width; LF_ERR_INVALID_ARG for a NULL planes[s] or y[s] or an nside
+ * other than 1 or 2.
+ * The per-plane formats (d = 24, d = 4096) may hold any planes in {-1, 0, 1}, not only the digits
+ * of one number: every output is defined per plane as above. Nothing is range-checked and the
+ * decomposition-overflow flag is never raised here.
+ * It reads no state of any earlier step (a context that has never run a step gives the same bits)
+ * and is asynchronous on the context's stream. It overwrites the context's operand rows, so the
+ * state a step left for lf_dev_fold_combine / lf_dev_fold_step_finish is forgotten: those then
+ * take the NTT-form fold from the f_k rows. */
+int lf_dev_commit_planes(lf_ctx *ctx, const lf_ajtai *aj, const lf_params *pr, const uint64_t *const *planes,
+                         int nside, size_t N, uint64_t *const *y, uint64_t *const *cm, uint64_t *const *wk);
 /* commit(z) followed by the commit+fold arithmetic of fold(), all on device */
 int lf_dev_fold_step(lf_ctx *ctx, const lf_ajtai *aj, const lf_params *pr, size_t W,
                      const lf_fold_step_bufs *b);

@@ -420,6 +420,23 @@ class Context:
         self.check(self.lib.lf_dev_fold_planes(self.h, C.byref(params), _dptr(planes0), _dptr(planes1), N,
                                                _dptr(rho), _dptr(f0_coeff), _dptr(f0), _dptr(w_ccs0)))
 
+    def dev_commit_planes(self, scheme: "AjtaiCommitmentScheme", params: LfParams, planes, N: int, y, cm=None,
+                          wk=None):
+        """commit_witnesses from the packed digit planes alone (lf_dev_commit_planes): planes, y, cm, wk
+        are sequences of one or two sides' device buffers (cm, wk, or single entries of them, may be
+        None): y[s] [K][kappa], cm[s] [kappa] = sum_k 2^k y[s][k], wk[s] [K][N / L]. Asynchronous"""
+        nside = len(planes)
+
+        def table(bufs, what):
+            if bufs is None:
+                return None
+            if len(bufs) != nside:
+                raise ValueError(f"{what}: one entry per side")
+            return (C.c_void_p * max(nside, 1))(*[_dptr(b) if b is not None else None for b in bufs])
+
+        self.check(self.lib.lf_dev_commit_planes(self.h, scheme.h, C.byref(params), table(planes, "planes"), nside, N,
+                                                 table(y, "y"), table(cm, "cm"), table(wk, "wk")))
+
     def dev_get_fhat(self, d, f_coeff, N, nv, out):
         """Witness::get_fhat on the device: out [tau][2^nv][d] from f_coeff [N][d]"""
         self.check(self.lib.lf_dev_get_fhat(self.h, d, _dptr(f_coeff), N, nv, _dptr(out)))

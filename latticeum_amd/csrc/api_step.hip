@@ -731,6 +731,100 @@ int lf_dev_fold_planes(lf_ctx *c, const lf_params *pr, const uint64_t *planes0, 
   return LF_OK;
 }
 
+// commit_witnesses from the packed planes alone: each fused decomposition's from-planes
+// front end (FusedSides::planes_in) writes all K planes of every side as operand rows
+// s K + k -- plane 0 too, as row_p0 -- and one contraction over A gives every y[s][k].
+// Nothing here depends on an earlier step; the operand buffer and the dead flags are
+// overwritten, so whatever step the context remembered is forgotten first.
+int lf_dev_commit_planes(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, const uint64_t *const *planes, int nside,
+                         size_t N, uint64_t *const *y, uint64_t *const *cm, uint64_t *const *wk) {
+  if (!c) return LF_ERR_INVALID_ARG;
+  DevGuard g(c);
+  if (!aj || !planes || !y) return fail(c, LF_ERR_INVALID_ARG, "commit_planes: NULL pointer");
+  if (nside < 1 || nside > 2) return fail(c, LF_ERR_INVALID_ARG, "commit_planes: nside is 1 or 2");
+  int lb, lbs;
+  LF_TRY(check_params(c, pr, lb, lbs));
+  if (!lf_fold_step_planes_len(pr, 1))
+    return fail(c, LF_ERR_UNSUPPORTED_RING, "commit_planes: d = 24, 16 .. 512, 1024 or 4096, b_small = 2, K <= 15");
+  if (pr->d != aj->d) return fail(c, LF_ERR_INVALID_ARG, "params ring != Ajtai ring");
+  for (int s = 0; s < nside; s++)
+    if (!planes[s] || !y[s]) return fail(c, LF_ERR_INVALID_ARG, "commit_planes: NULL planes or y");
+  const int d = pr->d, L = pr->L, K = pr->K;
+  if (N % L) return fail(c, LF_ERR_INCORRECT_LENGTH, "N must be a multiple of L");
+  if (N != aj->ncols) return fail(c, LF_ERR_INCORRECT_LENGTH, "N != Ajtai width");
+  Tables *t;
+  LF_TRY(get_tables(c, d, t));
+  // the decomposition a lean step of this scheme would run, and its refusal where it has none
+  uint64_t some;
+  lf_fold_step_bufs lean{};
+  lean.planes[0] = lean.planes[1] = &some;  // never dereferenced: step_plan reads which buffers are given
+  const Decomp dec = step_plan(aj, pr, lbs, t, &lean).dec;
+  if (dec == Decomp::Plain)
+    return fail(c, LF_ERR_INVALID_ARG,
+                "packed planes: d = 24 or the fused d = 16 .. 512 / 1024 / 4096 paths, b_small = 2, both sides");
+  if (dec == Decomp::Fused24 && (L - 1) * lb >= 62)
+    return fail(c, LF_ERR_INVALID_ARG, "packed Phi_72 planes need the wave-local decomposition");
+  c->step = {};  // its operand rows, flags and packed scratch are not a step's any more
+  if (!N) return LF_OK;
+  const size_t kappa = aj->kappa, kd = kappa * (size_t)d;
+  const int nvec = nside * K;
+  LF_TRY(grow(c, c->frag, c->frag_elems, lfk::frag_elems(aj->geom, d)));
+  LF_TRY(grow_dead(c, (size_t)aj->geom.nch * 64));
+  lfk::FusedSides sd{};
+  lfk::OutPtrs dst{};
+  uint32_t rows = 0;
+  sd.nside = nside;
+  sd.prepacked = (1 << nside) - 1;
+  sd.dead = c->dead;
+  for (int s = 0; s < nside; s++) {
+    sd.f_coeff[s] = nullptr;
+    sd.f_coeff_k[s] = sd.f_k[s] = nullptr;
+    sd.w_ccs_k[s] = wk ? wk[s] : nullptr;
+    sd.row_p0[s] = lfk::planes_row(s, K, 0);
+    sd.row0[s] = lfk::planes_row(s, K, 1);
+    // the packed format of this ring (digitpack.hpp): the masks at d = 24, else words or bytes
+    sd.masks[s] = reinterpret_cast<uint2 *>(const_cast<uint64_t *>(planes[s]));
+    sd.smg[s] = reinterpret_cast<uint32_t *>(const_cast<uint64_t *>(planes[s]));
+    for (int k = 0; k < K; k++) {
+      rows |= 1u << lfk::planes_row(s, K, k);
+      dst.p[lfk::planes_row(s, K, k)] = y[s] + (size_t)k * kd;
+    }
+  }
+  const lfk::DeadUnits dead{c->dead, rows};
+  {
+    PhaseTimer pt(c, LF_PHASE_DECOMPOSE);  // every side in one launch
+    switch (dec) {
+      case Decomp::Fused1024:
+        LF_HIP(c, lfk::decompose_fused(sd, N, lb, L, K, t->fwd, c->frag, aj->geom.nch, c->d_err, c->sink, c->ncu,
+                                       c->cur));
+        break;
+      case Decomp::Fused4k:
+        LF_HIP(c, lfk::decompose_n4k(sd, N, lb, L, K, nullptr, t->fwd, c->d_err, c->sink, c->ncu, c->cur, c->frag,
+                                     aj->geom.nch));
+        break;
+      case Decomp::FusedPow2:
+        LF_HIP(c, lfk::decompose_pow2(sd, N, d, lb, L, K, t->fwd, c->frag, aj->geom.nch, c->d_err, c->cur));
+        break;
+      default:  // Fused24
+        LF_HIP(c, lfk::decompose_phi72_sides(sd, N, lb, L, lbs, K, c->d_err, c->frag, aj->geom.nch, c->cur));
+        break;
+    }
+  }
+  LF_TRY(grow(c, c->scratch, c->scratch_elems, partial_elems(aj, nvec)));
+  hipEvent_t ea = nullptr, eb = nullptr;
+  if (c->timing) {
+    LF_HIP(c, hipEventCreate(&ea));
+    LF_HIP(c, hipEventCreate(&eb));
+  }
+  lfk::VecPtrs vp{};
+  LF_HIP(c, lfk::ajtai_mfma(aj->Af, aj->kr, kappa, aj->geom, d, vp, nvec, true, c->frag, c->scratch, nullptr, c->cur, ea,
+                            eb, &dst, &dead, c->zero80));
+  if (c->timing) c->pending.push_back({ea, eb, nvec});
+  for (int s = 0; s < nside && cm; s++)
+    if (cm[s]) LF_HIP(c, lfk::cm_from_y(y[s], kappa, d, lbs, K, cm[s], c->cur));
+  return LF_OK;
+}
+
 int lf_dev_fold_step(lf_ctx *c, const lf_ajtai *aj, const lf_params *pr, size_t W, const lf_fold_step_bufs *b) {
   DevGuard g(c);
   int lb, lbs;

@@ -190,11 +190,15 @@ __global__ void k_pack_sm24(FusedSides sd, size_t N, int K, int *err) {
 
 // NTM: streaming stores, bit 0 f_coeff_k, bit 1 f_k, bit 2 operand pieces; bit 3:
 // packed planes only -- no u64 f_coeff_k / f_k rows, the decomposed witnesses
-// stay as the digit masks (lf_fold_step_bufs.planes, lf_dev_expand_planes)
+// stay as the digit masks (lf_fold_step_bufs.planes, lf_dev_expand_planes); bit 4
+// (with bit 3): the masks are the input (sd.masks, read as mask24_digit reads them)
+// instead of made from the packed words, and plane 0 is an operand row too: row0 - 1,
+// which the launcher requires row_p0 to be (the row arithmetic of the other variants as it is)
 template <int NTM>
 __global__ void __launch_bounds__(256) k_decompose_phi72_w(FusedSides sd, size_t N, int lb, int L, int K, int *err,
                                                           uint4 *frag, int nch, size_t nblk) {
-  constexpr bool ROWS = !(NTM & 8);
+  constexpr bool ROWS = !(NTM & 8), PL = (NTM & 16) != 0;
+  constexpr int KMIN = PL ? 0 : 1;  // the first plane with an operand row
   __shared__ uint64_t lds_all[4 * PW_WAVE_U64];
   const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
   uint64_t *S = lds_all + wib * PW_WAVE_U64;
@@ -214,7 +218,7 @@ __global__ void __launch_bounds__(256) k_decompose_phi72_w(FusedSides sd, size_t
   // this lane's operand task: plane kq_t, virtual slot PW_VS r + vl_t, digit half hf_t
   const int kq_t = lane >> 4, vl_t = (lane & 3) | ((lane >> 3 & 1) << 2), hf_t = lane >> 2 & 1;
   const int k_t = 4 * pass + kq_t;
-  const bool emit = frag && k_t >= 1 && k_t < K;
+  const bool emit = frag && k_t >= KMIN && k_t < K;
   // this lane's row pieces: piece (64 it + lane) % 12 of the row of source lane
   // (64 it + lane) / 12, it < 12. The lane index goes through an empty asm at
   // each use, so these per-piece offsets are recomputed (a few integer
@@ -228,7 +232,13 @@ __global__ void __launch_bounds__(256) k_decompose_phi72_w(FusedSides sd, size_t
   uint32_t nzm[8], ngm[8];
   for (int l = L - 1; l >= 0; l--) {
     uint32_t nz = 0, ng = 0;
-    if (ok && kok) {  // plane k of the 24 packed sign|magnitude coefficients (k_pack_sm24)
+    if constexpr (PL) {
+      if (ok && kok) {  // the caller's masks: bits 24..31 dropped, a sign without a digit dropped (mask24_digit)
+        const uint2 m = sd.masks[side][mask24_index(k, N, g * L + l)];
+        nz = m.x & 0xFFFFFFu;
+        ng = m.y & nz;
+      }
+    } else if (ok && kok) {  // plane k of the 24 packed sign|magnitude coefficients (k_pack_sm24)
       const uint4 *src = reinterpret_cast<const uint4 *>(sd.smg[side] + sm24_word(g * L + l, 0));
 #pragma unroll
       for (int q = 0; q < 3; q++) {
@@ -246,7 +256,7 @@ __global__ void __launch_bounds__(256) k_decompose_phi72_w(FusedSides sd, size_t
         nzm[q] = nz;
         ngm[q] = ng;
       }
-    if (sd.masks[side] && ok && kok) sd.masks[side][mask24_index(k, N, g * L + l)] = make_uint2(nz, ng);
+    if (!PL && sd.masks[side] && ok && kok) sd.masks[side][mask24_index(k, N, g * L + l)] = make_uint2(nz, ng);
     // f_coeff_k rows from the owners' masks
     if constexpr (ROWS) {
     const int ln0 = opaque_lane();
@@ -294,7 +304,7 @@ __global__ void __launch_bounds__(256) k_decompose_phi72_w(FusedSides sd, size_t
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the tile is read before the operand rounds reuse it
     }
     const size_t u = frag_pos(G, l, L, frag_ptop(frag_groups(W), L));  // position of these 16 columns' unit
-    if (frag && sd.dead && gi == 0 && k >= 1 && k < K)  // one lane per plane writes its flag
+    if (frag && sd.dead && gi == 0 && k >= KMIN && k < K)  // one lane per plane writes its flag
       sd.dead[u * 32 + row0 + k - 1] = ((bal >> (16 * kq)) & 0xFFFFull) ? 0 : 1;
     if (frag && (bal || !sd.dead)) {
       const int ch = (int)(u >> 1), uh = (int)(u & 1);
@@ -326,7 +336,7 @@ __global__ void __launch_bounds__(256) k_decompose_phi72_w(FusedSides sd, size_t
       }
     }
   }
-  {  // w_ccs_k = CRT(sum_l B^l D_l), rows w_ccs_k[k][16 G ..] through the tile
+  if (!PL || w_ccs_k) {  // w_ccs_k = CRT(sum_l B^l D_l), rows w_ccs_k[k][16 G ..] through the tile (PL: may be null)
     uint64_t c[24];
 #pragma unroll
     for (int i = 0; i < 24; i++) {
@@ -372,9 +382,17 @@ hipError_t decompose_phi72_sides(const FusedSides &sd, size_t N, int lb, int L, 
   }
   bool packed_sm = K <= 15;  // the wave kernel reads k_pack_sm24's 16-bit words
   for (int s = 0; s < sd.nside; s++) packed_sm &= sd.smg[s] != nullptr;
-  if (lbs == 1 && L <= 8 && (L - 1) * lb < 62 && packed_sm) {
+  // from the caller's masks (lf_dev_commit_planes): the wave-local kernel or nothing
+  const bool pl = sd.planes_in();
+  if (pl) {
+    if (lbs != 1 || L > 8 || (L - 1) * lb >= 62 || K > 15 || !frag) return hipErrorInvalidValue;
+    for (int s = 0; s < sd.nside; s++)
+      if (!sd.masks[s] || sd.f_k[s] || sd.f_coeff_k[s] || sd.row_p0[s] < 0 || sd.row_p0[s] != sd.row0[s] - 1)
+        return hipErrorInvalidValue;
+  }
+  if (lbs == 1 && L <= 8 && (L - 1) * lb < 62 && (packed_sm || pl)) {
     const size_t nblk = (W + 15) / 16, waves = (size_t)sd.nside * nblk * ((K + 3) / 4);
-    {
+    if (!pl) {
       const size_t np = (size_t)sd.nside * N * SM24_WORDS;
       hipLaunchKernelGGL(k_pack_sm24, dim3(blocks(np, 256)), dim3(256), 0, st, sd, N, K, err);
     }
@@ -395,16 +413,16 @@ hipError_t decompose_phi72_sides(const FusedSides &sd, size_t N, int lb, int L, 
     if (none) {
       for (int s = 0; s < sd.nside; s++)
         if (!sd.masks[s]) return hipErrorInvalidValue;
-      ntm = 12;  // packed only (bit 3), the operand rows still streamed
+      ntm = pl ? 28 : 12;  // packed only (bit 3), the operand rows still streamed; bit 4: from the masks
     }
     const dim3 grid(blocks(waves, 4));
 #define LF_PW(M)                                                                                          \
   case M:                                                                                                \
     hipLaunchKernelGGL(k_decompose_phi72_w<M>, grid, dim3(256), 0, st, sd, N, lb, L, K, err, frag, nch, nblk); \
     break;
-    switch (ntm) { LF_PW(7) LF_PW(12) default: return hipErrorInvalidValue; }
+    switch (ntm) { LF_PW(7) LF_PW(12) LF_PW(28) default: return hipErrorInvalidValue; }
 #undef LF_PW
-    if (masks_written) *masks_written = sd.masks[0] != nullptr && (sd.nside < 2 || sd.masks[1] != nullptr);
+    if (masks_written) *masks_written = !pl && sd.masks[0] != nullptr && (sd.nside < 2 || sd.masks[1] != nullptr);
     if (dead_written) *dead_written = frag && sd.dead;  // the wave-local kernel flags its zero units
     return hipGetLastError();
   }

@@ -42,7 +42,9 @@ struct P2 {
 
 using P2Degrees = std::integer_sequence<int, 16, 32, 64, 128, 256, 512>;
 
-template <int D, bool NT>
+// PL (lf_dev_commit_planes): the words are loaded from sd.smg (the caller's packed planes)
+// instead of made from f_coeff -- nothing to range-check, nothing to write back
+template <int D, bool NT, bool PL>
 __global__ void __launch_bounds__(P2<D>::NTH) k_decompose_pow2(size_t N, int L, int lb, int K, FusedSides sd,
                                                               ring::NegaTables fwd, uint4 *frag, int nch,
                                                               int *err) {
@@ -65,8 +67,15 @@ __global__ void __launch_bounds__(P2<D>::NTH) k_decompose_pow2(size_t N, int L, 
 #pragma unroll
     for (int l = 0; l < P2_LMAX; l++) {
       if (l >= L) continue;
-      const uint64_t *src = sd.f_coeff[side] + (e0 + l) * D;
       uint32_t m = 0;
+      if constexpr (PL) {
+#pragma unroll
+        for (int q = 0; q < PH; q++) {
+          sm[l][q] = ok ? sd.smg[side][smp2_word(e0 + l, D, t + q * T)] : 0;
+          m |= sm[l][q];
+        }
+      } else {
+      const uint64_t *src = sd.f_coeff[side] + (e0 + l) * D;
 #pragma unroll
       for (int q = 0; q < PH; q++) {
         const int i = t + q * T;
@@ -79,6 +88,7 @@ __global__ void __launch_bounds__(P2<D>::NTH) k_decompose_pow2(size_t N, int L, 
         sm[l][q] = smp2_make(lo, hi);
         if (ok) sd.smg[side][smp2_word(e0 + l, D, i)] = sm[l][q];
         m |= sm[l][q];
+      }
       }
       m = (m | (m >> 16)) & SM16_MAG;
       if (m) atomicOr(&mags[l], m);
@@ -152,7 +162,7 @@ __global__ void __launch_bounds__(P2<D>::NTH) k_decompose_pow2(size_t N, int L, 
         }
         if (live) __syncthreads();  // the tile is read before the next unit's digits overwrite it
       }
-      if (ok) {
+      if (ok && (!PL || sd.w_ccs_k[side])) {  // from planes: w_ccs_k may be null
         uint64_t *ow = sd.w_ccs_k[side] + ((size_t)k * W + g) * D;
 #pragma unroll
         for (int q = 0; q < PER; q++) ow[t + q * T] = acc[q];
@@ -182,7 +192,7 @@ hipError_t decompose_pow2(const FusedSides &sd, size_t N, int d, int lb, int L, 
     return hipErrorInvalidValue;
   int nrows = 1;  // the operand rows, plus the u64 rows the caller keeps
   for (int s = 0; s < sd.nside; s++) {
-    if (!sd.smg[s] || !sd.f_coeff[s] || !sd.w_ccs_k[s]) return hipErrorInvalidValue;
+    if (!sd.smg[s] || (!sd.planes_in() && (!sd.f_coeff[s] || !sd.w_ccs_k[s]))) return hipErrorInvalidValue;
     if (sd.row0[s] < 0 || sd.row0[s] + K - 1 > 32 || sd.row_p0[s] >= 32) return hipErrorInvalidValue;
     nrows = std::max(nrows, 1 + (sd.f_k[s] ? 1 : 0) + (sd.f_coeff_k[s] ? 1 : 0));
   }
@@ -192,12 +202,15 @@ hipError_t decompose_pow2(const FusedSides &sd, size_t N, int d, int lb, int L, 
   const bool nt = dec_streaming(sd.nside * (size_t)K * N * d * 8 * nrows, /*refold=*/true);
   return nega_degree_in(d, [&](auto dd) {
     constexpr int D = decltype(dd)::value;
-    if (nt)
-      hipLaunchKernelGGL((k_decompose_pow2<D, true>), dim3(grid_cap(units)), dim3(P2<D>::NTH), 0, st, N, L, lb, K, sd,
-                         fwd, frag, nch, err);
-    else
-      hipLaunchKernelGGL((k_decompose_pow2<D, false>), dim3(grid_cap(units)), dim3(P2<D>::NTH), 0, st, N, L, lb, K, sd,
-                         fwd, frag, nch, err);
+#define LF_P2(NT_, PL_)                                                                                             \
+  hipLaunchKernelGGL((k_decompose_pow2<D, NT_, PL_>), dim3(grid_cap(units)), dim3(P2<D>::NTH), 0, st, N, L, lb, K, sd, \
+                     fwd, frag, nch, err)
+    if (sd.planes_in()) {
+      if (nt) LF_P2(true, true); else LF_P2(false, true);
+    } else {
+      if (nt) LF_P2(true, false); else LF_P2(false, false);
+    }
+#undef LF_P2
     return hipGetLastError();
   }, P2Degrees{});
 }

@@ -131,4 +131,14 @@ LF_HD int sm8_digit(uint32_t byte, int b) {
   return ((byte >> (4 + b)) & 1u) ? -bit : bit;
 }
 
+// ---------------------------------------------------------------- launches that start from the public planes
+// A fused decomposition whose every side (nside = 1 or 2) is already packed -- one bit per
+// side in FusedSides::prepacked -- reads the caller's planes and no coefficients
+// (lf_dev_commit_planes). All K planes of side s are then operand rows of their own, plane 0
+// first: row s K + k, so plane 0's row is the one before plane 1's and 2 K <= 30 rows are used.
+LF_HD bool planes_all_packed(int prepacked, int nside) {
+  return nside >= 1 && nside <= 2 && prepacked == (1 << nside) - 1;
+}
+LF_HD int planes_row(int side, int K, int k) { return side * K + k; }
+
 }  // namespace lfk

@@ -29,6 +29,22 @@ hipError_t commit_y0(const uint64_t *cm, uint64_t *y, size_t kappa, int d, int l
   return hipGetLastError();
 }
 
+// the other way round: cm = sum_{k>=0} b^k y_k from all K planes' commitments (lf_dev_commit_planes)
+__global__ void k_cm_from_y(const uint64_t *y, size_t n, int lbs, int K, uint64_t *cm) {
+  size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  if (c >= n) return;
+  uint64_t acc = 0;
+  for (int k = K - 1; k >= 1; k--) acc = gl::mul_pow2(gl::add(acc, y[(size_t)k * n + c]), lbs);
+  cm[c] = gl::add(y[c], acc);
+}
+
+hipError_t cm_from_y(const uint64_t *y, size_t kappa, int d, int lbs, int K, uint64_t *cm, hipStream_t st) {
+  size_t n = kappa * (size_t)d;
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_cm_from_y, dim3(blocks(n, 256)), dim3(256), 0, st, y, n, lbs, K, cm);
+  return hipGetLastError();
+}
+
 // both sides' y_0 and the folded commitment in one pass (see kernels.hpp y0_cm0)
 // one thread per commitment slot; K <= Y0_KMAX: every plane's y and rho of a side
 // are loaded before the Horner chain, so the 2 (K - 1) loads of a thread are in

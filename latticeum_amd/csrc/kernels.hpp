@@ -72,6 +72,8 @@ hipError_t ajtai_commit(const uint64_t *A, size_t kappa, size_t ncols, int d, co
                         hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 hipError_t commit_y0(const uint64_t *cm, uint64_t *y, size_t kappa, int d, int lbs, int K,
                      hipStream_t st);
+// cm = sum_{k>=0} 2^(k lbs) y[k] over the K planes' commitments y [K][kappa] (canonical in and out)
+hipError_t cm_from_y(const uint64_t *y, size_t kappa, int d, int lbs, int K, uint64_t *cm, hipStream_t st);
 // the NTT-form linear fold (fold.hip)
 hipError_t fold(const uint64_t *rho, const VecPtrs &x, int nwit, size_t n, int d, uint64_t *out,
                 hipStream_t st, const int *run_if = nullptr);
@@ -197,8 +199,12 @@ struct FusedSides {
   uint32_t *smg[2] = {nullptr, nullptr};         // the packed digits (digitpack.hpp): d = 1024 fused and d = 24 the
                                                  // sign|magnitude words, d = 4096 fused the digit bytes
   uint8_t *dead = nullptr;                       // d = 1024 fused: dead-unit flags of the rows written (DeadUnits)
-  int prepacked = 0;                             // d = 1024 fused: bit s = side s's smg is already written
-                                                 // (from_w_ccs wrote it; only side 1 may be)
+  int prepacked = 0;                             // bit s = side s's packed digits are already written. 2 (d = 1024
+                                                 // fused, nside = 2): from_w_ccs wrote side 1's words. Every side's
+                                                 // bit (planes_in below): the launch starts from the caller's planes
+                                                 // in smg (d = 24: in masks) -- no f_coeff is read, nothing is packed
+                                                 // or range-checked, and plane 0 is emitted as row_p0 at every ring
+  bool planes_in() const { return planes_all_packed(prepacked, nside); }
 };
 // f_0 = sum_v rho_v f_v with every f_v read from the D8 operand rows (k_fold_frag)
 struct FoldRows {
@@ -218,7 +224,8 @@ hipError_t decompose_fused(const FusedSides &sd, size_t N, int lb, int L, int K,
 // sign|magnitude words (digitpack.hpp smp2_*) into sd.smg[s] (required), w_ccs_k, the
 // f_coeff_k / f_k rows where given, and the planes' operand rows (row0 / row_p0 of
 // sd, Lp = L order, offset form) straight into frag; sd.dead (may be null) gets the
-// flag of every (position, row) the launch owns. K <= 15, L <= 8.
+// flag of every (position, row) the launch owns. K <= 15, L <= 8. sd.planes_in(): sd.smg[s]
+// is the input (the caller's planes) and f_coeff is not read; w_ccs_k may then be null.
 hipError_t decompose_pow2(const FusedSides &sd, size_t N, int d, int lb, int L, int K, const ring::NegaTables &fwd,
                           uint4 *frag, int nch, int *err, hipStream_t st);
 // the packed words of N elements -> f_coeff_k [K][N][d] (digits mod p)
@@ -293,7 +300,9 @@ hipError_t flag_to_err(const int *flag, int *err, int bit, hipStream_t st);
 // d = 24: both sides of a fold step in one launch (blockIdx.z = side); frag as decompose_witness
 // *masks_written: whether the launch filled sd.masks (the wave-local kernel does);
 // *dead_written: whether it left zero units unwritten and flagged them in sd.dead
-// (the wave-local kernel with frag and sd.dead; the block kernel writes every row)
+// (the wave-local kernel with frag and sd.dead; the block kernel writes every row).
+// sd.planes_in(): sd.masks[s] is the input, all K planes become operand rows (row_p0 =
+// row0 - 1), w_ccs_k may be null; only where the wave-local kernel runs, else an error
 hipError_t decompose_phi72_sides(const FusedSides &sd, size_t N, int lb, int L, int lbs, int K, int *err,
                                  uint4 *frag, int nch, hipStream_t st, bool *masks_written = nullptr,
                                  bool *dead_written = nullptr);
@@ -318,6 +327,8 @@ hipError_t expand_sm8(const uint32_t *sm8, size_t N, int K, uint64_t *fck, hipSt
 // d = 4096, b_small = 2: sm4 holds nside N SM4_WORDS Morton words (digitpack.hpp); sink 4096 words.
 // With frag (a scheme whose geometry has Lp = L and qperm), planes k >= 1 are also
 // written as operand rows row0[side] + k - 1, as decompose_fused does for d = 1024.
+// sd.planes_in() (both this and decompose_fused): sd.smg[s] is the input, nothing is packed
+// or range-checked, and w_ccs_k may be null.
 hipError_t decompose_n4k(const FusedSides &sd, size_t N, int lb, int L, int K, uint64_t *sm4,
                          const ring::NegaTables &fwd, int *err, uint64_t *sink, int ncu, hipStream_t st,
                          uint4 *frag = nullptr, int nch = 0);

@@ -662,7 +662,8 @@ __device__ __forceinline__ void mid3_stage(int2 *mid3, const uint64_t *mid3_g) {
     mid3[q] = make_int2((int)(uint32_t)m, (int)(uint32_t)(m >> 32));
   }
 }
-template <bool NT>
+// WKOPT (lf_dev_commit_planes without wk): a side's w_ccs_k may be null
+template <bool NT, bool WKOPT = false>
 __global__ void __launch_bounds__(512, 1) k_decompose_fused(size_t N, int L, int lb,
                                                            int K, FusedSides sd, const uint64_t *az_g,
                                                            uint4 *frag, int nch,
@@ -805,7 +806,7 @@ __global__ void __launch_bounds__(512, 1) k_decompose_fused(size_t N, int L, int
           }
         }
       }
-      if (ok) {
+      if (ok && (!WKOPT || w_ccs_k)) {
         uint64_t *ow = w_ccs_k + ((size_t)kb * W + g) * D + r;
 #pragma unroll
         for (int i = 0; i < 32; i++) out_store<NT>(&ow[32 * n32::brv5(i)], gl::canon(acc[i]));
@@ -839,11 +840,13 @@ hipError_t decompose_fused(const FusedSides &sd, size_t N, int lb, int L, int K,
   if (K > 15 || !fwd.mid || !sink || ncu < 1 || sd.nside < 1 || sd.nside > 2) return hipErrorInvalidValue;
   for (int s = 0; s < sd.nside; s++)
     if (!sd.smg[s]) return hipErrorInvalidValue;
-  // sides whose words from_w_ccs already wrote (only side 1, the step's new witness) are not re-packed
-  if ((sd.prepacked & ~2) || ((sd.prepacked & 2) && sd.nside != 2)) return hipErrorInvalidValue;
+  // sides whose words are already written are not re-packed: side 1 alone (from_w_ccs wrote
+  // the step's new witness), or every side (the caller's planes, lf_dev_commit_planes)
+  if (sd.prepacked && sd.prepacked != 2 && !sd.planes_in()) return hipErrorInvalidValue;
+  if ((sd.prepacked & 2) && sd.nside != 2) return hipErrorInvalidValue;
   FusedSides sp = sd;
   if (sd.prepacked & 2) sp.nside = 1;  // side 0 only
-  {
+  if (!sd.planes_in()) {
     const size_t words = sp.nside * N * SM1024_WORDS;
     hipLaunchKernelGGL(k_pack_sm, dim3(blocks(words / 4, 256)), dim3(256), 0, st, sp, N, K, err);
   }
@@ -856,7 +859,16 @@ hipError_t decompose_fused(const FusedSides &sd, size_t N, int lb, int L, int K,
   // outputs: f_coeff_k, f_k, frag (each K N D words per side) and w_ccs_k
   const size_t out_bytes = sd.nside * (size_t)K * N * D * 8 * 3;
   if (!fwd.az) return hipErrorInvalidValue;
-  if (dec_streaming(out_bytes, false))
+  bool wkopt = false;  // a side without w_ccs_k: only from the caller's planes
+  for (int s = 0; s < sd.nside; s++) wkopt |= !sd.w_ccs_k[s];
+  if (wkopt && !sd.planes_in()) return hipErrorInvalidValue;
+  if (wkopt && dec_streaming(out_bytes, false))
+    hipLaunchKernelGGL((k_decompose_fused<true, true>), dim3(grid), dim3(512), 0, st, N, L, lb, K, sd, fwd.az, frag,
+                       nch, sink);
+  else if (wkopt)
+    hipLaunchKernelGGL((k_decompose_fused<false, true>), dim3(grid), dim3(512), 0, st, N, L, lb, K, sd, fwd.az, frag,
+                       nch, sink);
+  else if (dec_streaming(out_bytes, false))
     hipLaunchKernelGGL(k_decompose_fused<true>, dim3(grid), dim3(512), 0, st, N, L, lb, K, sd, fwd.az, frag,
                        nch, sink);
   else

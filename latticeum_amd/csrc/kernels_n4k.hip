@@ -192,7 +192,8 @@ __global__ void k_pack_sm8(FusedSides sd, size_t N, int K, int *err) {
   }
 }
 
-template <bool NT>
+// WKOPT (both fused kernels; lf_dev_commit_planes without wk): a side's w_ccs_k may be null
+template <bool NT, bool WKOPT = false>
 __global__ void __launch_bounds__(512, 1) k_decompose_n4k_fused(size_t N, int L, int lb, int K,
                                                                FusedSides sd, const uint64_t *mid_fg,
                                                                const uint64_t *tw_g, const uint64_t *ztab_g,
@@ -316,9 +317,11 @@ __global__ void __launch_bounds__(512, 1) k_decompose_n4k_fused(size_t N, int L,
         __syncthreads();  // S consumed before the next transpose
       }
     }
+    if (!WKOPT || sd.w_ccs_k[side]) {
     uint64_t *ow = (ok ? sd.w_ccs_k[side] + ((size_t)kb * W + g) * D4 : sink) + m0 + 4 * r;
 #pragma unroll
     for (int i = 0; i < 32; i++) ow[128 * n32::brv5(i)] = gl::canon(acc[i]);
+    }
   }
 }
 
@@ -397,7 +400,7 @@ __device__ __forceinline__ void midq_apply(const uint64_t *midl, uint64_t *y0, u
   }
 }
 
-template <bool NT>
+template <bool NT, bool WKOPT = false>
 __global__ void __launch_bounds__(512, 1) k_decompose_n4k_mx(size_t N, int L, int lb, int K, FusedSides sd,
                                                             const uint64_t *midq_g, const uint64_t *zq_g,
                                                             uint4 *frag, int nch, uint64_t *sink) {
@@ -506,9 +509,11 @@ __global__ void __launch_bounds__(512, 1) k_decompose_n4k_mx(size_t N, int L, in
         }
       }
     }
+    if (!WKOPT || sd.w_ccs_k[side]) {
     uint64_t *ow = (ok ? sd.w_ccs_k[side] + ((size_t)kb * W + g) * D4 : sink) + m0 + 4 * r;
 #pragma unroll
     for (int i = 0; i < 32; i++) ow[128 * n32::brv5(i)] = gl::canon(acc[i]);
+    }
   }
 }
 
@@ -768,8 +773,13 @@ hipError_t decompose_n4k(const FusedSides &sd, size_t N, int lb, int L, int K, u
       refold |= sd.f_k[s] != nullptr;
     }
     if (ncu < 32) return hipErrorInvalidValue;
-    const size_t threads = sd.nside * N * SM8_PLANE_WORDS;  // one per word of a plane
-    hipLaunchKernelGGL(k_pack_sm8, dim3(blocks(threads, 256)), dim3(256), 0, st, s8, N, K, err);
+    if (sd.planes_in()) {  // the caller's bytes are read as they are (lf_dev_commit_planes)
+      for (int s = 0; s < sd.nside; s++)
+        if (!sd.smg[s]) return hipErrorInvalidValue;
+    } else {
+      const size_t threads = sd.nside * N * SM8_PLANE_WORDS;  // one per word of a plane
+      hipLaunchKernelGGL(k_pack_sm8, dim3(blocks(threads, 256)), dim3(256), 0, st, s8, N, K, err);
+    }
     // 32 blocks per group of 8 units (8 XCDs x 4 quarters), one block per CU
     const unsigned grid = (unsigned)(ncu / 32 * 32);
     // outputs: f_coeff_k, f_k, the operand rows (each K N d words per side) and w_ccs_k
@@ -782,7 +792,24 @@ hipError_t decompose_n4k(const FusedSides &sd, size_t N, int lb, int L, int K, u
     }();
     bool mx = fwd.zq && fwd.midq && !valu;
     for (int s = 0; s < sd.nside; s++) mx = mx && !sd.f_coeff_k[s];
-    if (mx) {
+    bool wkopt = false;  // a side without w_ccs_k: only from the caller's planes
+    for (int s = 0; s < sd.nside; s++) wkopt |= !sd.w_ccs_k[s];
+    if (wkopt && !sd.planes_in()) return hipErrorInvalidValue;
+    if (wkopt && mx) {
+      if (nt)
+        hipLaunchKernelGGL((k_decompose_n4k_mx<true, true>), dim3(grid), dim3(512), 0, st, N, L, lb, K, s8, fwd.midq,
+                           fwd.zq, frag, nch, sink);
+      else
+        hipLaunchKernelGGL((k_decompose_n4k_mx<false, true>), dim3(grid), dim3(512), 0, st, N, L, lb, K, s8, fwd.midq,
+                           fwd.zq, frag, nch, sink);
+    } else if (wkopt) {
+      if (nt)
+        hipLaunchKernelGGL((k_decompose_n4k_fused<true, true>), dim3(grid), dim3(512), 0, st, N, L, lb, K, s8, fwd.mid,
+                           fwd.tw4, fwd.ztab, frag, nch, sink);
+      else
+        hipLaunchKernelGGL((k_decompose_n4k_fused<false, true>), dim3(grid), dim3(512), 0, st, N, L, lb, K, s8, fwd.mid,
+                           fwd.tw4, fwd.ztab, frag, nch, sink);
+    } else if (mx) {
       if (nt)
         hipLaunchKernelGGL(k_decompose_n4k_mx<true>, dim3(grid), dim3(512), 0, st, N, L, lb, K, s8, fwd.midq,
                            fwd.zq, frag, nch, sink);

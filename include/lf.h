@@ -378,7 +378,10 @@ typedef struct {
    * the operand rows only for a rho that is not short (lf_ctx_fold_flag).
    * d = 2048 has no packed form (sixteen elements' transform tile, 256 KiB, does
    * not fit a compute unit's LDS): planes, or NULL fk, are refused there as before.
-   * lf_fold_step_planes_len gives the length of one side's buffer. */
+   * lf_fold_step_planes_len gives the length of one side's buffer. Without a step,
+   * lf_dev_pack_planes writes a side's planes from its f_coeff, lf_dev_planes_witness
+   * gives f_coeff, f and w_ccs back from them, and lf_dev_planes_check tells whether a
+   * packer wrote the bytes. */
   uint64_t *planes[2];
 } lf_fold_step_bufs;
 /* u64 words of one side's `planes` buffer for N elements (host only, no context):
@@ -411,9 +414,55 @@ int lf_dev_expand_planes(lf_ctx *ctx, const lf_params *pr, const uint64_t *plane
  * clears the flag, lf_ctx_fold_flag gives 1, and the outputs are unspecified (nothing is read
  * or written out of bounds).
  * The commitments are not part of it: lf_dev_commit_planes makes the y_s[k] (and side 1's cm)
- * from the same planes, and cm_0 = sum_i rho_i y_i is lf_dev_fold over those 2K rows. */
+ * from the same planes, and cm_0 = sum_i rho_i y_i is lf_dev_fold over those 2K rows.
+ * The way in is lf_dev_pack_planes (also of f0_coeff, as the next fold's planes0), the way back
+ * lf_dev_planes_witness. */
 int lf_dev_fold_planes(lf_ctx *ctx, const lf_params *pr, const uint64_t *planes0, const uint64_t *planes1,
                        size_t N, const uint64_t *rho, uint64_t *f0_coeff, uint64_t *f0, uint64_t *w_ccs0);
+/* The three entries below take one side's packed digit planes without a step: no scheme, and
+ * they read and write no step state, operand row or dead flag (a lf_dev_fold_combine after them
+ * still completes the step before them; a context that has never run a step gives the same
+ * bits). Rings: wherever lf_fold_step_planes_len(pr, N) != 0 (d = 24, 16 .. 512, 1024, 4096;
+ * b_small = 2, K <= 15), else LF_ERR_UNSUPPORTED_RING. LF_ERR_INCORRECT_LENGTH for N = 0 or N
+ * not a multiple of L; LF_ERR_INVALID_ARG for a NULL pointer or a buffer that is not 16-byte
+ * aligned. All buffers are device memory.
+ *
+ * lf_dev_pack_planes: f_coeff [N][d] canonical words -> planes (lf_fold_step_planes_len(pr, N)
+ * words, every one written: the buffer need not be cleared). The bytes are those a lean
+ * lf_dev_fold_step leaves in planes[s] for a side with these coefficients: digit k of x is
+ * sign(x) bit_k(|x|) -- sm16 words at d = 16 .. 512 and 1024, masks with bits 24..31 zero at
+ * d = 24, bytes with the coefficient's sign on every plane at d = 4096. A coefficient with
+ * |x| >= 2^K raises the context's decomposition-overflow flag as the step does: the next
+ * lf_ctx_sync returns LF_ERR_DECOMPOSITION_OVERFLOW and clears it; the planes are then
+ * unspecified (nothing is written outside the buffer). Asynchronous on the context's stream. */
+int lf_dev_pack_planes(lf_ctx *ctx, const lf_params *pr, const uint64_t *f_coeff, size_t N, uint64_t *planes);
+/* planes -> the undecomposed witness: f_coeff[e][i] = sum_(k < K) 2^k digit_k(e, i) in canonical
+ * form (a negative sum as p - |x|), with the digits decoded exactly as lf_dev_expand_planes
+ * decodes them -- total on any byte string; at the per-plane formats (d = 24, d = 4096) the
+ * planes need not be the digits of one number. f [N] and w_ccs [N / L] are what
+ * lf_dev_witness_from_f_coeff gives for that f_coeff. Any of the three outputs may be NULL, not
+ * all three. The planes are read once and no [K][N][d] u64 row is allocated or written: f and
+ * w_ccs come from a second pass over f_coeff, and an output the caller does not take is kept in
+ * a scratch of the context ([N][d] words). Raises no flag. Asynchronous. */
+int lf_dev_planes_witness(lf_ctx *ctx, const lf_params *pr, const uint64_t *planes, size_t N, uint64_t *f_coeff,
+                          uint64_t *f, uint64_t *w_ccs);
+/* Are these bytes a packer's, and how large is the witness: one pass over the planes, nothing
+ * of size K N d allocated; synchronises the stream. *norm: always the l_inf norm of the
+ * coefficients lf_dev_planes_witness gives. The planes are canonical iff
+ * lf_dev_pack_planes(lf_dev_planes_witness(planes)) == planes byte for byte, which is:
+ *   sm16 halves (d = 16 .. 512, 1024): magnitude bits K .. 14 are zero and the half is not
+ *     0x8000 (a negative zero);
+ *   d = 24: bits 24..31 of both words are zero, and per coefficient the planes with a set sign
+ *     bit are none or exactly the planes with a nonzero digit;
+ *   d = 4096: per coefficient quad bits 4..7 are equal on all K planes, and a set sign bit of
+ *     quarter b has some plane with bit b set.
+ * LF_OK with *fault = LF_PLANES_OK, or LF_ERR_VERIFICATION with *fault = LF_PLANES_ENCODING and
+ * *where = the lowest element index that holds a non-canonical entry, or (bound != 0,
+ * *norm > bound, and no encoding fault) LF_PLANES_BOUND and *where = the lowest element with a
+ * coefficient above the bound. */
+enum lf_planes_fault { LF_PLANES_OK = 0, LF_PLANES_ENCODING = 1, LF_PLANES_BOUND = 2 };
+int lf_dev_planes_check(lf_ctx *ctx, const lf_params *pr, const uint64_t *planes, size_t N, uint64_t bound,
+                        uint64_t *norm, int *fault, size_t *where);
 /* decompose_witness's commitments (commit_witnesses, decomposition.rs:178-201) from the packed
  * digit planes alone: for each side s < nside (1 or 2) and plane k < K,
  *   y[s][k] = A · NTT(D_(s,k))                    [K][kappa] ring elements, canonical

@@ -437,6 +437,30 @@ class Context:
         self.check(self.lib.lf_dev_commit_planes(self.h, scheme.h, C.byref(params), table(planes, "planes"), nside, N,
                                                  table(y, "y"), table(cm, "cm"), table(wk, "wk")))
 
+    def dev_pack_planes(self, params: LfParams, f_coeff, N: int, planes):
+        """f_coeff [N][d] -> one side's packed digit planes (lf_dev_pack_planes; fold_step_planes_len words,
+        every one written). Asynchronous; a coefficient with |x| >= 2^K makes the next sync() raise
+        LF_ERR_DECOMPOSITION_OVERFLOW"""
+        self.check(self.lib.lf_dev_pack_planes(self.h, C.byref(params), _dptr(f_coeff), N, _dptr(planes)))
+
+    def dev_planes_witness(self, params: LfParams, planes, N: int, f_coeff=None, f=None, w_ccs=None):
+        """packed digit planes -> the undecomposed witness (lf_dev_planes_witness): f_coeff = sum_k 2^k digit_k,
+        f = CRT(f_coeff) [N] and w_ccs [N / L]; any of the three may be None, not all. Asynchronous"""
+        opt = lambda b: _dptr(b) if b is not None else None
+        self.check(self.lib.lf_dev_planes_witness(self.h, C.byref(params), _dptr(planes), N, opt(f_coeff), opt(f),
+                                                  opt(w_ccs)))
+
+    def dev_planes_check(self, params: LfParams, planes, N: int, bound: int = 0):
+        """(norm, fault, where) of lf_dev_planes_check: the l_inf norm of the planes' coefficients, and
+        PLANES_OK, PLANES_ENCODING (where = the lowest element no packer wrote) or PLANES_BOUND (bound != 0:
+        where = the lowest element with a coefficient above it). A fault raises nothing; a refusal raises LfError"""
+        norm, fault, where = C.c_uint64(0), C.c_int(0), C.c_size_t(0)
+        rc = self.lib.lf_dev_planes_check(self.h, C.byref(params), _dptr(planes), N, bound, C.byref(norm),
+                                          C.byref(fault), C.byref(where))
+        if rc != ERR_VERIFICATION:
+            self.check(rc)
+        return norm.value, fault.value, where.value
+
     def dev_get_fhat(self, d, f_coeff, N, nv, out):
         """Witness::get_fhat on the device: out [tau][2^nv][d] from f_coeff [N][d]"""
         self.check(self.lib.lf_dev_get_fhat(self.h, d, _dptr(f_coeff), N, nv, _dptr(out)))
@@ -1159,6 +1183,7 @@ class VerificationError(LfError):
 
 ERR_NOT_SATISFIED = 14  # lf.h LF_ERR_NOT_SATISFIED
 ERR_VERIFICATION = 12  # lf.h LF_ERR_VERIFICATION
+PLANES_OK, PLANES_ENCODING, PLANES_BOUND = range(3)  # lf.h lf_planes_fault
 MEMLOG_OK, MEMLOG_INDEX, MEMLOG_VALUE, MEMLOG_OPENING, MEMLOG_TRANSITION = range(5)  # lf.h lf_memlog_check
 REL_WITNESS_F, REL_WITNESS_W, REL_NORM, REL_CM, REL_V, REL_U, REL_CCS = range(1, 8)  # lf.h lf_relation_check
 RELATION_CHECKS = {REL_WITNESS_F: "f != CRT(f_coeff)", REL_WITNESS_W: "w_ccs != from_f(f).w_ccs",

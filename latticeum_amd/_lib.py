@@ -208,6 +208,9 @@ SIGNATURES = {
     "lf_dev_fold_planes": (I, [VP, C.POINTER(LfParams), VP, VP, SZ, VP, VP, VP, VP]),
     "lf_dev_commit_planes": (I, [VP, VP, C.POINTER(LfParams), C.POINTER(VP), I, SZ, C.POINTER(VP), C.POINTER(VP),
                                  C.POINTER(VP)]),
+    "lf_dev_pack_planes": (I, [VP, C.POINTER(LfParams), VP, SZ, VP]),
+    "lf_dev_planes_witness": (I, [VP, C.POINTER(LfParams), VP, SZ, VP, VP, VP]),
+    "lf_dev_planes_check": (I, [VP, C.POINTER(LfParams), VP, SZ, U64, C.POINTER(U64), C.POINTER(I), C.POINTER(SZ)]),
     "lf_ccs_create": (I, [VP, I, I, SZ, SZ, VP, VP, VP, I, C.POINTER(VP)]),
     "lf_ccs_destroy": (None, [VP]),
     "lf_ccs_set_structure": (I, [VP, VP, SZ, I, I, VP, VP, VP, I]),

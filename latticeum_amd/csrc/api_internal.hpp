@@ -97,6 +97,8 @@ struct lf_ctx {
   size_t sel_elems = 0;
   uint64_t *rel = nullptr;      // relation checks: the first unsatisfied row per z, the norm
   size_t rel_elems = 0;
+  uint64_t *pwit = nullptr;     // lf_dev_planes_witness: the outputs the caller does not take ([N][d] words each)
+  size_t pwit_elems = 0;
   uint64_t *hmsg = nullptr;     // pinned host staging of the sumcheck round messages
   size_t hmsg_elems = 0;
   uint8_t *mv_host = nullptr;   // lf_memtree_verify / lf_memtree_audit: one chunk's pinned staging

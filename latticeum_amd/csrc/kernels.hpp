@@ -323,6 +323,19 @@ hipError_t expand_phi72(const uint2 *planes, size_t n, uint64_t *fc, uint64_t *f
 hipError_t expand_sm(const uint32_t *smg, size_t N, int K, uint64_t *fck, hipStream_t st);
 // d = 4096 (kernels_n4k.hip): the fused decomposition's digit bytes -> f_coeff_k [K][N][4096]
 hipError_t expand_sm8(const uint32_t *sm8, size_t N, int K, uint64_t *fck, hipStream_t st);
+// the two fused decompositions' pack kernels alone, one side: f_coeff [N] -> the public words (d = 1024) / bytes
+// (d = 4096); err: a coefficient with |x| >= 2^K
+hipError_t pack_sm(const uint64_t *f_coeff, size_t N, int K, uint32_t *smg, int *err, hipStream_t st);
+hipError_t pack_sm8(const uint64_t *f_coeff, size_t N, int K, uint32_t *sm8, int *err, hipStream_t st);
+// ---------------------------------------------------------------- packed planes <-> witness (planes_witness.hip)
+// One side's public planes (lf_fold_step_planes_len words) at d = 24, 16 .. 512, 1024, 4096, K <= 15; every
+// buffer 16-byte aligned. pack: f_coeff [N][d] -> planes, every word written; err as above. recompose:
+// f_coeff[e][i] = sum_k 2^k digit_k(e, i) in canonical form, decoded as the expanders decode. scan: res[0] =
+// the l_inf norm of those values, res[1] = the lowest element with an entry no packer writes, res[2] = the
+// lowest element with a value above bound (bound != 0), all-ones for none (three device words)
+hipError_t planes_pack(const uint64_t *fc, size_t N, int d, int K, uint64_t *planes, int *err, hipStream_t st);
+hipError_t planes_recompose(const uint64_t *planes, size_t N, int d, int K, uint64_t *fc, hipStream_t st);
+hipError_t planes_scan(const uint64_t *planes, size_t N, int d, int K, uint64_t bound, uint64_t *res, hipStream_t st);
 // ---------------------------------------------------------------- d = 4096 on the quarter transforms (kernels_n4k.hip)
 // d = 4096, b_small = 2: sm4 holds nside N SM4_WORDS Morton words (digitpack.hpp); sink 4096 words.
 // With frag (a scheme whose geometry has Lp = L and qperm), planes k >= 1 are also

@@ -835,6 +835,16 @@ hipError_t expand_sm(const uint32_t *smg, size_t N, int K, uint64_t *fck, hipStr
 }
 
 // ---------------------------------------------------------------- launchers
+// k_pack_sm alone, one side: f_coeff -> the sign|magnitude words (lf_dev_pack_planes)
+hipError_t pack_sm(const uint64_t *f_coeff, size_t N, int K, uint32_t *smg, int *err, hipStream_t st) {
+  if (!N) return hipSuccess;
+  if (K < 1 || K > 15) return hipErrorInvalidValue;
+  FusedSides sd{};
+  sd.nside = 1;
+  sd.f_coeff[0] = f_coeff, sd.smg[0] = smg;
+  hipLaunchKernelGGL(k_pack_sm, dim3(blocks(N * SM1024_WORDS / 4, 256)), dim3(256), 0, st, sd, N, K, err);
+  return hipGetLastError();
+}
 hipError_t decompose_fused(const FusedSides &sd, size_t N, int lb, int L, int K, const ring::NegaTables &fwd, uint4 *frag, int nch, int *err, uint64_t *sink, int ncu,
                            hipStream_t st) {
   if (K > 15 || !fwd.mid || !sink || ncu < 1 || sd.nside < 1 || sd.nside > 2) return hipErrorInvalidValue;

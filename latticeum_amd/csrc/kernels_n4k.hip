@@ -757,6 +757,17 @@ hipError_t from_w_ccs_n4k(const uint64_t *w_ccs, size_t W, int lb, int L, uint64
   return hipGetLastError();
 }
 
+// k_pack_sm8 alone, one side: f_coeff -> the digit bytes (lf_dev_pack_planes)
+hipError_t pack_sm8(const uint64_t *f_coeff, size_t N, int K, uint32_t *sm8, int *err, hipStream_t st) {
+  if (!N) return hipSuccess;
+  if (K < 1 || K > 15) return hipErrorInvalidValue;
+  FusedSides sd{};
+  sd.nside = 1;
+  sd.f_coeff[0] = f_coeff, sd.smg[0] = sm8;
+  hipLaunchKernelGGL(k_pack_sm8, dim3(blocks(N * SM8_PLANE_WORDS, 256)), dim3(256), 0, st, sd, N, K, err);
+  return hipGetLastError();
+}
+
 hipError_t decompose_n4k(const FusedSides &sd, size_t N, int lb, int L, int K, uint64_t *sm4,
                          const ring::NegaTables &fwd, int *err, uint64_t *sink, int ncu, hipStream_t st, uint4 *frag,
                          int nch) {

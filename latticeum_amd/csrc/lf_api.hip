@@ -393,6 +393,7 @@ lf_ctx::~lf_ctx() {
   if (c->ptrs) (void)hipFree(c->ptrs);
   if (c->sel) (void)hipFree(c->sel);
   if (c->rel) (void)hipFree(c->rel);
+  if (c->pwit) (void)hipFree(c->pwit);
   if (c->hmsg) (void)hipHostFree(c->hmsg);
   if (c->mv_host) (void)hipHostFree(c->mv_host);
   if (c->mv_dev) (void)hipFree(c->mv_dev);
